@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of the DAFNe inference hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N=1)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]          (N=1)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, ONE timed region of exactly K steps
+(ms_per_step x K = that region), the JSON line.  --dump-outputs DIR writes the detections the timed path returned for its last
+timed step (dump_outputs).  --full adds the rest: 5 timed regions (value = the median one), the timed path against its
+immediate form, and the extra objects listed below.
 
 One step = one pass of the whole path over one batch of synthetic 1024x1024 BGR
 uint8 tiles that already sit in HBM: normalise/pad -> ResNet-FPN -> DAFNe head ->
@@ -21,7 +26,7 @@ DOTA-1.0 head: 15 classes, THRESH_WITH_CTR, SORT_CORNERS).  configs[1] (R50-FPN,
 batch 8, one GPU) is measured in the same run at N=1 and reported under
 "configs1_r50_b8".  Random-init weights (seeded), synthetic images.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only):
   roofline      dominant kernel = the kernel with the most GPU time per step (whole batch on one stream: every launch
                 has the GPU to itself, the layout `--mode serial` runs and profiles/r04b_kernel_stats_isolated.txt
                 profiles with rocprofv3): algorithmic FLOPs of its launches / their HIP-event time vs the dense bf16
@@ -550,6 +555,26 @@ def headline(args, world, dt, det_mean, region_times=None):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, rows, counts):
+    """--dump-outputs: what a caller of the timed path receives for the last timed step -> path/detections.npy ([N, k_cap, 18]
+    float32 rows, the layout of postprocess.rows_to_instances; rows at and past an image's count are zeroed, the engine leaves them
+    unwritten) and path/counts.npy ([N] float32).  Inputs and weights are seeded, so two builds can be compared file for file.
+    Beyond DUMP_LIMIT_BYTES only the first images are written (the same images every run)."""
+    os.makedirs(path, exist_ok=True)
+    r = rows.float().cpu().numpy()
+    c = counts.cpu().numpy().astype(np.int64)
+    n = max(1, min(r.shape[0], DUMP_LIMIT_BYTES // max(r[0].nbytes, 1)))
+    r, c = r[:n].copy(), c[:n]
+    for i, k in enumerate(c):
+        r[i, k:] = 0
+    np.save(os.path.join(path, "detections.npy"), r.astype(np.float32))
+    np.save(os.path.join(path, "counts.npy"), c.astype(np.float32))
+    return {"images": int(n), "files": ["detections.npy", "counts.npy"]}
+
+
 _TELEMETRY_DIR = {}
 
 
@@ -730,13 +755,22 @@ def parse_args(argv=None):
     ap.add_argument("--no-defer", action="store_true",
                     help="pipelined mode: every step's decode + NMS enqueued right behind its own convolutions (round 3's form) instead "
                          "of at the next step's head towers (detect_packed(defer=True)); for A/B runs")
-    ap.add_argument("--regions", type=int, default=5,
-                    help="timed regions of --steps steps each, back to back; value = the median region, value_min / value_max beside it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline profile pass, R50 and NMS side metrics")
-    ap.add_argument("--no-energy", action="store_true", help="skip the per-kernel energy ledger (about 45 s of looped kernels)")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of --steps steps each, back to back; value = the median region, value_min / value_max beside it "
+                         "(default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: 5 timed regions, the timed path against its immediate form, roofline and "
+                         "per-kernel profiles, energy ledger, NMS and other-config side metrics, CPU baseline and equivalence AP")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's detections as DIR/detections.npy and DIR/counts.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and equivalence AP")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip roofline profile pass, R50 and NMS side metrics")
+    ap.add_argument("--no-energy", action="store_true", help="--full: skip the per-kernel energy ledger (about 45 s of looped kernels)")
     ap.add_argument("--energy-seconds", type=float, default=2.0, help="telemetry window per ledger entry (after a 1-s lead-in)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
+    return args
 
 
 def _free_port():
@@ -831,6 +865,7 @@ def _run_worker(args, make_step, rank, world, distributed, device):
     batch = torch.randint(0, 256, (args.batch, 3, args.size, args.size), generator=g, dtype=torch.uint8).to(device)
 
     gathered = {"out": None}
+    latest = {"res": None}          # (rows, counts) of the latest step whose post-process has been enqueued
 
     def step():
         # decode + NMS + gather (+ the RCCL detection gather) ride a side stream and overlap the
@@ -840,6 +875,7 @@ def _run_worker(args, make_step, rank, world, distributed, device):
             rows, counts = model.detect_packed(batch)
             if distributed:
                 gathered["out"] = gather_detections(rows, counts, dst=0)
+            latest["res"] = (rows, counts)
             return rows, counts
         # the loop's form of the pipelined step: this call's convolutions, then the PREVIOUS call's decode + NMS, which start on
         # the side stream when this call's sub-batches reach their head towers (detect_packed(defer=True)); flush() completes the
@@ -849,9 +885,11 @@ def _run_worker(args, make_step, rank, world, distributed, device):
         return after(model.detect_packed(batch, pipelined=True, splits=args.splits, defer=True))
 
     def after(res):
-        if res is not None and distributed:
-            with torch.cuda.stream(model.side_stream):
-                gathered["out"] = gather_detections(res[0], res[1], dst=0)
+        if res is not None:
+            latest["res"] = res
+            if distributed:
+                with torch.cuda.stream(model.side_stream):
+                    gathered["out"] = gather_detections(res[0], res[1], dst=0)
         return res
 
     def flush():
@@ -863,14 +901,16 @@ def _run_worker(args, make_step, rank, world, distributed, device):
     tel0 = device_telemetry(local_rank)
     dt, region_times = time_regions(step, args.steps, args.warmup, distributed, args.regions, device, per_rank=per_rank, flush_fn=flush)
     tel1 = device_telemetry(local_rank)
-    last = step()
-    rows, counts = flush() if (args.mode != "serial" and not args.no_defer) else (last if args.mode != "serial" else step())
+    # the last timed step's detections: time_steps' flush inside the timed region handed them to after() (every mode)
+    rows, counts = latest["res"]
     torch.cuda.synchronize()
     out = headline(args, world, dt, float(counts.float().mean().item()), region_times)
     out["config"]["mode"] = args.mode
+    if args.dump_outputs and rank == 0:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, *(gathered["out"] if distributed else (rows, counts)))
     # the path that was just timed against the immediate form of the same step, OUTSIDE the timed region (the parity tests pin
     # both to the oracle at this size: tests/test_gpu_headline.py::test_headline_timed_layout_vs_oracle)
-    if args.mode != "serial":
+    if args.full and args.mode != "serial":
         ri, ci = model.detect_packed(batch, pipelined=True, splits=args.splits)
         torch.cuda.synchronize()
         out["timed_path_equals_immediate"] = bool(torch.equal(ci, counts) and all(
@@ -878,7 +918,7 @@ def _run_worker(args, make_step, rank, world, distributed, device):
     out["device_telemetry"] = {"before_timed_regions": tel0, "after_timed_regions": tel1}
     out["distributed"] = distributed_record(args, world, distributed, per_rank, gathered["out"])
     # extras only at N=1: at N>1 the other ranks would sit in the final barrier while rank 0 measures side metrics
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
       try:
         if args.mode == "serial":
             model.detect_packed(batch, pipelined=True, splits=args.splits)     # builds the timed layout's plans for the profile
@@ -1207,7 +1247,7 @@ def _run_worker(args, make_step, rank, world, distributed, device):
                 torch.cuda.synchronize()
       except Exception as e:      # noqa: BLE001  (the headline line is printed regardless)
         out.setdefault("side_metric_errors", {})["extras"] = "%s: %s" % (type(e).__name__, e)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             keep = {"fp32": [], "bf16_emulation": []} if not args.no_extras else None
             out["cpu_baseline"] = cpu_baseline(cfg, sd, args.depth, keep=keep)

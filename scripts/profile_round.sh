@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU-box call (through gpurun) that produces the round's measurement evidence under gpurun_out/<tag>/:
-#   bench.json                 default bench.py line (pipelined layout, all extras)
+#   bench.json                 bench.py --full line (pipelined layout, all extras)
 #   kernel_stats_isolated.txt  rocprofv3 --kernel-trace --stats of `bench.py --mode serial` (whole batch, one stream)
 #   kernel_stats_pipelined.txt the same for the default (timed) layout
 #   pmc_isolated/              PMC passes (FETCH_SIZE / WRITE_SIZE / MFMA busy) of the serial layout
@@ -10,7 +10,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
-python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp; export TMPDIR=/tmp
 for mode in serial pipelined; do
   rm -rf $OUT/prof_$mode

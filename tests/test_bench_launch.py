@@ -87,8 +87,50 @@ def test_plain_command_self_launches_two_ranks():
     assert abs(out["value"] - 8 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
 
 
+def test_plain_run_times_exactly_steps():
+    """A plain run (no --full, no --regions): one timed region of exactly K steps, ms_per_step x K = that region."""
+    lines = _run(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["stub"]["calls_rank0"] == 2 + 4 + 1           # W + K + the recorded step: no further timed region
+    assert out["steps"] == 4 and out["regions"]["count"] == 1 and out["regions"]["steps_each"] == 4
+    assert out["ms_per_step"] >= 19.0                         # the stub's 20 ms per step
+    assert abs(out["value"] - 8 * 4 / (out["ms_per_step"] * 4e-3)) < 1e-6 * out["value"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+
+
+def test_full_and_dump_options():
+    import bench
+    a = bench.parse_args(["--steps", "3"])
+    assert a.regions == 1 and not a.full and a.dump_outputs is None
+    assert bench.parse_args(["--full"]).regions == 5
+    assert bench.parse_args(["--full", "--regions", "2"]).regions == 2
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path, monkeypatch):
+    """--dump-outputs: [N, k_cap, 18] float32 rows with everything at and past an image's count zeroed (the engine leaves those
+    rows unwritten) and the counts as float32; beyond the size limit the first images only."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    rows = torch.randn(3, 5, 18, generator=g)
+    counts = torch.tensor([2, 0, 5], dtype=torch.int32)
+    rec = bench.dump_outputs(str(tmp_path / "d"), rows, counts)
+    r = np.load(tmp_path / "d" / "detections.npy")
+    c = np.load(tmp_path / "d" / "counts.npy")
+    assert rec["images"] == 3 and r.dtype == np.float32 and c.dtype == np.float32 and r.shape == (3, 5, 18)
+    assert c.tolist() == [2.0, 0.0, 5.0]
+    assert np.array_equal(r[0, :2], rows[0, :2].numpy()) and not r[0, 2:].any() and not r[1].any()
+    assert np.array_equal(r[2], rows[2].numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 5 * 18 * 4)
+    assert bench.dump_outputs(str(tmp_path / "e"), rows, counts)["images"] == 2
+    assert np.load(tmp_path / "e" / "detections.npy").shape == (2, 5, 18)
+
+
 def test_value_is_the_median_of_several_timed_regions():
-    """--regions R (default 5): R back-to-back regions of exactly K steps, each bracketed by barrier + synchronize and reduced
+    """--regions R (default 1; 5 with --full): R back-to-back regions of exactly K steps, each bracketed by barrier + synchronize and reduced
     with MAX over the ranks; `value` / `ms_per_step` are the MEDIAN region's (ms_per_step x steps is one measured region),
     value_min / value_max and every region's figure sit beside it; the warm-up runs once."""
     lines = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--regions", "3"])

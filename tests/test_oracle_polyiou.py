@@ -1,6 +1,9 @@
 """CPU: the C restatement (oracle/poly_oracle.c) against the reference's known
 answers, the committed golden vectors (made from the reference's own compiled
 polyiou.cpp) and, when present, oracle/_ref itself."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
@@ -31,16 +34,20 @@ def test_golden_pairs_bit_exact(golden):
     assert np.array_equal(got, g["iou"]), "fp64 IoU must match the reference bit for bit"
 
 
-def test_against_compiled_reference_if_present():
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref not built here")
-    rng = np.random.default_rng(5)
-    p = rrects(20000, rng, extent=300.0).astype(np.float64)
-    q = rrects(20000, rng, extent=300.0).astype(np.float64)
-    assert np.array_equal(oracle.iou_poly_pairs(p, q), oracle.ref_iou_poly_pairs(p, q))
-    p = rng.normal(0, 5, (20000, 8))
-    q = rng.normal(0, 5, (20000, 8))          # self-intersecting / arbitrary quads
-    assert np.array_equal(oracle.iou_poly_pairs(p, q), oracle.ref_iou_poly_pairs(p, q))
+def test_against_compiled_reference_if_present(golden):
+    """Rotated rectangles, then self-intersecting / arbitrary quads: bit-equal to the reference's own answers stored in
+    tests/golden/ref_iou_pairs.npz (make_golden_ref_pairs.py) and, where oracle/_ref is built, to the library itself."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_golden_ref_pairs as mg
+    g = golden("ref_iou_pairs")
+    live = oracle.ref_lib() is not None
+    for i, (p, q) in enumerate(mg.pairs()):
+        assert np.array_equal(p[:4], g["p_head_%d" % i]) and np.array_equal(q[:4], g["q_head_%d" % i]), "seeded inputs changed"
+        assert np.array_equal(p.sum(0), g["p_sum_%d" % i]) and np.array_equal(q.sum(0), g["q_sum_%d" % i]), "seeded inputs changed"
+        got = oracle.iou_poly_pairs(p, q)
+        assert np.array_equal(got, g["iou_%d" % i])
+        if live:
+            assert np.array_equal(got, oracle.ref_iou_poly_pairs(p, q))
 
 
 def test_f32_entry_equals_widened():
