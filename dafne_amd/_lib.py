@@ -30,7 +30,14 @@ class LevelDesc(ctypes.Structure):
 class DecodeParams(ctypes.Structure):
     _fields_ = [("n_images", c_i32), ("n_levels", c_i32), ("n_classes", c_i32),
                 ("pre_nms_topk", c_i32), ("pre_nms_thresh", c_float), ("thresh_with_ctr", c_i32),
-                ("sort_corners", c_i32), ("m_cap", c_i32)]
+                ("sort_corners", c_i32), ("m_cap", c_i32), ("flags", c_i32)]
+
+
+DECODE_NO_CENTER, DECODE_NO_CTRNESS = 1, 2       # dafne_decode_params.flags (include/dafne_amd.h)
+
+
+class ChainSeg(ctypes.Structure):
+    _fields_ = [("d_t", c_void_p), ("d_out", c_void_p), ("H", c_i32), ("W", c_i32)]
 
 
 class ConvSeg(ctypes.Structure):
@@ -71,6 +78,7 @@ SIGNATURES = {
     "dafne_decode_levels_hip": (c_int, [ctypes.POINTER(DecodeParams), ctypes.POINTER(LevelDesc)] +
                                 [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
     "dafne_sort_quadrilateral_hip": (c_int, [c_void_p, c_void_p, c_i64, c_void_p]),
+    "dafne_corner_chain_hip": (c_int, [ctypes.POINTER(ChainSeg), c_int, c_int, c_int, c_void_p, c_void_p]),
     "dafne_gather_detections_hip": (c_int, [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                                              c_void_p]),
     "dafne_conv2d_nhwc_bf16_hip": (c_int, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg), c_void_p]),

@@ -47,6 +47,7 @@ struct LevelDev {
 struct DecodeDev {
     LevelDev lv[kMaxLevels];
     int n_images, n_levels, C, topk, twc, sortc, m_cap;
+    int no_center, no_ctr;   // DAFNE_DECODE_NO_CENTER / _NO_CTRNESS
     float thresh;
     unsigned key_lo;   // score bits are keyed as (bits - key_lo)
     int shift;         // histogram bin = key >> shift
@@ -69,6 +70,11 @@ __device__ __forceinline__ bool score_of(const DecodeDev& P, const LevelDev& L, 
                                          float& score, float& ctr_out) {
     const size_t px = (size_t)img * L.H * L.W + loc;
     float cls = sigmoidf_ref(L.logits[px * L.logits_ps + c]);
+    if (P.no_ctr) {          // CENTERNESS none (dafne_outputs.py:810-829): no sqrt, no centerness factor, THRESH_WITH_CTR moot
+        ctr_out = 1.0f;
+        score = cls;
+        return cls > P.thresh;
+    }
     float ctr = sigmoidf_ref(L.ctrness[px * L.ctrness_ps]);
     ctr_out = ctr;
     bool cand;
@@ -442,12 +448,16 @@ __global__ void __launch_bounds__(kFinThreads) decode_finalize_kernel(
         const float ly = (float)(y * L.stride) + half;
         const size_t px = (size_t)img * L.H * L.W + loc;
         const float* dl = L.delta + px * L.delta_ps;
-        const float* ce = L.center + px * L.center_ps;
-        const float cx = ce[0], cy = ce[1];
+        float cx = 0.f, cy = 0.f;
+        if (!P.no_center) {
+            const float* ce = L.center + px * L.center_ps;
+            cx = ce[0]; cy = ce[1];
+        }
         float q[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            float reg = ((j & 1) ? cy : cx) + dl[j];     // dafne.py:403  center.repeat + delta
+            // dafne.py:403  center.repeat + delta; direct / offset / iterative heads (no center): the regression itself
+            float reg = P.no_center ? dl[j] : ((j & 1) ? cy : cx) + dl[j];
             reg = reg * L.scale;                         // dafne.py:406  Scale
             reg = reg * fs;                              // dafne_outputs.py:771-772
             q[j] = ((j & 1) ? ly : lx) + reg;            // dafne_outputs.py:861-873
@@ -458,7 +468,7 @@ __global__ void __launch_bounds__(kFinThreads) decode_finalize_kernel(
 #pragma unroll
             for (int j = 0; j < 8; j++) o_corners[row * 8 + j] = q[j];
             o_scores[row] = score;
-            o_ctr[row] = sigmoidf_ref(L.ctrness[px * L.ctrness_ps]);
+            o_ctr[row] = P.no_ctr ? 1.0f : sigmoidf_ref(L.ctrness[px * L.ctrness_ps]);
             o_classes[row] = c;
             o_locs[row * 2 + 0] = lx;
             o_locs[row * 2 + 1] = ly;
@@ -554,13 +564,18 @@ int setup(DecodeDev& D, const dafne_decode_params* prm, const dafne_level_desc* 
     D.n_images = prm->n_images; D.n_levels = prm->n_levels; D.C = prm->n_classes;
     D.topk = prm->pre_nms_topk; D.twc = prm->thresh_with_ctr; D.sortc = prm->sort_corners;
     D.m_cap = prm->m_cap; D.thresh = prm->pre_nms_thresh;
+    if (prm->flags & ~(DAFNE_DECODE_NO_CENTER | DAFNE_DECODE_NO_CTRNESS))
+        return dafne::fail(DAFNE_E_INVALID, "decode: unknown flags 0x%x", (unsigned)prm->flags);
+    D.no_center = (prm->flags & DAFNE_DECODE_NO_CENTER) != 0;
+    D.no_ctr = (prm->flags & DAFNE_DECODE_NO_CTRNESS) != 0;
     // key = bits - key_lo, top bin index < 2048.  THRESH_WITH_CTR: the ranked score IS the thresholded one, so
     // scores lie in (max(thresh,0), 1] and the key range starts at the threshold.  Otherwise the candidate test is
     // cls > thresh while the ranked score is sqrt(cls * ctr), anywhere in (0, 1] (dafne_outputs.py:812-829): the
     // key range must start at 0, or every score below the threshold would collapse into one key and top-k would
     // pick among them by flat index instead of by score.
     union { float f; unsigned u; } t, one;
-    t.f = (prm->thresh_with_ctr && prm->pre_nms_thresh > 0.f) ? prm->pre_nms_thresh : 0.f;
+    // (without centerness the ranked score is the thresholded sigmoid(cls): the key range starts at the threshold too)
+    t.f = ((prm->thresh_with_ctr || D.no_ctr) && prm->pre_nms_thresh > 0.f) ? prm->pre_nms_thresh : 0.f;
     one.f = 1.0f;
     D.key_lo = t.u < one.u ? t.u : 0u;
     unsigned range = one.u - D.key_lo;
@@ -620,7 +635,7 @@ int dafne_decode_levels_hip(const dafne_decode_params* prm, const dafne_level_de
     if (!d_corners || !d_scores || !d_ctr || !d_classes || !d_locs || !d_levels || !d_hbox || !d_counts)
         return dafne::fail(DAFNE_E_INVALID, "decode: null output");
     for (int l = 0; l < D.n_levels; l++)
-        if (!D.lv[l].logits || !D.lv[l].delta || !D.lv[l].center || !D.lv[l].ctrness)
+        if (!D.lv[l].logits || !D.lv[l].delta || (!D.no_center && !D.lv[l].center) || (!D.no_ctr && !D.lv[l].ctrness))
             return dafne::fail(DAFNE_E_INVALID, "decode: null input at level %d", l);
     hipStream_t st = (hipStream_t)stream;
     size_t zbytes = (size_t)((char*)(D.e_cnt + (size_t)D.n_images * D.n_levels) - (char*)D.hist);

@@ -1,5 +1,5 @@
 // HBM-bound companions of the conv kernel (gfx950): image normalisation into the
-// stem layout, 3x3/s2 max-pool, GroupNorm finalize/apply(+ReLU), ReLU copy.
+// stem layout, 3x3/s2 max-pool, GroupNorm finalize/apply(+ReLU), ReLU copy, the iterative head's corner chain.
 //
 // Reference call sites: OneStageDetector.preprocess_image
 // (dafne/modeling/one_stage_detector.py:100-107), d2 BasicStem max_pool2d
@@ -267,6 +267,120 @@ inline unsigned grid_for(long long total) {
     return (unsigned)(b < 1 ? 1 : (b > 256 * 8 ? 256 * 8 : b));
 }
 
+
+// Iterative corner chain (CORNER_PREDICTION iterative, dafne.py:381-387): c_k = c{k}_pred(cat(tower, c0..c_{k-1})).  The
+// tower half of every c{k}_pred (with its bias) is one prediction conv over the corners tower, T[..., 2k:2k+2]; what is
+// left is three dependent 3x3 stencils over 2, 4 and 6 channels, in fp32:
+//   c0 = T0,  c1 = T1 + conv(c0; W1),  c2 = T2 + conv(c0,c1; W2),  c3 = T3 + conv(c0,c1,c2; W3).
+// One workgroup per 16x16 output tile of one (level, image); it recomputes the halos in LDS (c0 on tile+3, c1 on tile+2,
+// c2 on tile+1) instead of launching three times.  Every c_k is 0 outside the map (the reference pads the concatenated
+// input), so halo pixels outside the map are stored as 0, never computed.  T is only read: out-of-place by contract.
+constexpr int kChainTile = 16;
+constexpr int kChainMaxSegs = 8;
+constexpr int kChainWeights = 216;   // W1 [2][2][3][3], W2 [2][4][3][3], W3 [2][6][3][3] (OIHW, chain channels only)
+
+struct ChainSeg {
+    const float* t;
+    float* out;
+    int H, W, tiles_x, tile0;
+};
+struct ChainDev {
+    ChainSeg seg[kChainMaxSegs];
+    int n_segs, t_ps;
+    const float* w;
+};
+
+// one stage: region r_k = tile grown by (3 - k) on every side; c_j (j < k) lives on region r_j, (k - j) wider per side
+template <int K>
+__device__ __forceinline__ void chain_stage(const ChainDev& P, const ChainSeg& S, const float* __restrict__ T, int y0,
+                                            int x0, float* const* cj, float* __restrict__ dst, float* __restrict__ gout) {
+    constexpr int G = 3 - K;                          // halo of this stage's region
+    constexpr int RS = kChainTile + 2 * G;            // region side
+    const float* __restrict__ wk = P.w + (K == 1 ? 0 : K == 2 ? 36 : 108);   // [2][2K][3][3]
+    for (int i = threadIdx.x; i < RS * RS; i += blockDim.x) {
+        const int r = i / RS, c = i - r * RS;
+        const int y = y0 - G + r, x = x0 - G + c;
+        const bool inside = y >= 0 && y < S.H && x >= 0 && x < S.W;
+        float a0 = 0.f, a1 = 0.f;
+        if (inside) {
+            const float* tp = T + ((size_t)y * S.W + x) * P.t_ps + 2 * K;
+            a0 = tp[0];
+            a1 = tp[1];
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                const int js = kChainTile + 2 * (3 - j);  // side of c_j's region
+                const int off = K - j - 1;                // (r, c) of this stage -> top-left neighbour in region j
+#pragma unroll
+                for (int ch = 0; ch < 2; ch++) {
+                    const float* src = cj[2 * j + ch];
+#pragma unroll
+                    for (int ky = 0; ky < 3; ky++)
+#pragma unroll
+                        for (int kx = 0; kx < 3; kx++) {
+                            const float v = src[(r + off + ky) * js + (c + off + kx)];
+                            a0 += wk[((0 * 2 * K) + 2 * j + ch) * 9 + ky * 3 + kx] * v;
+                            a1 += wk[((1 * 2 * K) + 2 * j + ch) * 9 + ky * 3 + kx] * v;
+                        }
+                }
+            }
+        }
+        if (K == 3) {
+            if (inside)
+                *reinterpret_cast<float2*>(gout + ((size_t)y * S.W + x) * 8 + 6) = make_float2(a0, a1);
+        } else {
+            dst[i] = a0;
+            dst[RS * RS + i] = a1;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) corner_chain_kernel(ChainDev P) {
+    constexpr int R0 = kChainTile + 6, R1 = kChainTile + 4, R2 = kChainTile + 2;
+    __shared__ float s0[2 * R0 * R0], s1[2 * R1 * R1], s2[2 * R2 * R2];
+    int si = 0;
+    for (int k = 1; k < P.n_segs; k++)
+        if ((int)blockIdx.x >= P.seg[k].tile0) si = k;
+    const ChainSeg S = P.seg[si];
+    const int tl = blockIdx.x - S.tile0;
+    const int ty = tl / S.tiles_x;
+    const int y0 = ty * kChainTile, x0 = (tl - ty * S.tiles_x) * kChainTile;
+    const size_t img_px = (size_t)blockIdx.y * S.H * S.W;
+    const float* __restrict__ T = S.t + img_px * P.t_ps;
+    float* __restrict__ O = S.out + img_px * 8;
+    // c0 = T0 on tile+3 (0 outside the map)
+    for (int i = threadIdx.x; i < R0 * R0; i += blockDim.x) {
+        const int r = i / R0, c = i - r * R0;
+        const int y = y0 - 3 + r, x = x0 - 3 + c;
+        float a0 = 0.f, a1 = 0.f;
+        if (y >= 0 && y < S.H && x >= 0 && x < S.W) {
+            const float* tp = T + ((size_t)y * S.W + x) * P.t_ps;
+            a0 = tp[0];
+            a1 = tp[1];
+        }
+        s0[i] = a0;
+        s0[R0 * R0 + i] = a1;
+    }
+    __syncthreads();
+    float* cj[6] = {s0, s0 + R0 * R0, s1, s1 + R1 * R1, s2, s2 + R2 * R2};
+    chain_stage<1>(P, S, T, y0, x0, cj, s1, O);
+    __syncthreads();
+    chain_stage<2>(P, S, T, y0, x0, cj, s2, O);
+    __syncthreads();
+    chain_stage<3>(P, S, T, y0, x0, cj, nullptr, O);
+    // c0..c2 of the tile itself: the centres of their regions
+    for (int i = threadIdx.x; i < kChainTile * kChainTile; i += blockDim.x) {
+        const int r = i / kChainTile, c = i - r * kChainTile;
+        const int y = y0 + r, x = x0 + c;
+        if (y < S.H && x < S.W) {
+            float* op = O + ((size_t)y * S.W + x) * 8;
+            const int i0 = (r + 3) * R0 + c + 3, i1 = (r + 2) * R1 + c + 2, i2 = (r + 1) * R2 + c + 1;
+            *reinterpret_cast<float2*>(op + 0) = make_float2(s0[i0], s0[R0 * R0 + i0]);
+            *reinterpret_cast<float2*>(op + 2) = make_float2(s1[i1], s1[R1 * R1 + i1]);
+            *reinterpret_cast<float2*>(op + 4) = make_float2(s2[i2], s2[R2 * R2 + i2]);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -346,6 +460,28 @@ int dafne_relu_copy_bf16_hip(const void* d_in, void* d_out, int64_t n_elems, voi
     hipLaunchKernelGGL(relu_copy_kernel, dim3(grid_for(n_elems / 8)), dim3(256), 0, (hipStream_t)stream,
                        (const uint4*)d_in, (uint4*)d_out, (long long)(n_elems / 8));
     return dafne::check_launch("relu_copy");
+}
+
+int dafne_corner_chain_hip(const dafne_chain_seg* segs, int n_segs, int n_images, int t_ps, const float* d_w,
+                           void* stream) {
+    if (!segs || n_segs < 1 || n_segs > kChainMaxSegs || n_images < 1 || t_ps < 8 || !d_w)
+        return dafne::fail(DAFNE_E_INVALID, "corner_chain: bad args");
+    ChainDev D;
+    D.n_segs = n_segs; D.t_ps = t_ps; D.w = d_w;
+    long long tiles = 0;
+    for (int s = 0; s < n_segs; s++) {
+        const dafne_chain_seg& g = segs[s];
+        if (!g.d_t || !g.d_out || g.H < 1 || g.W < 1 || (const void*)g.d_t == (const void*)g.d_out)
+            return dafne::fail(DAFNE_E_INVALID, "corner_chain: segment %d", s);
+        ChainSeg& c = D.seg[s];
+        c.t = g.d_t; c.out = g.d_out; c.H = g.H; c.W = g.W;
+        c.tiles_x = (g.W + kChainTile - 1) / kChainTile;
+        c.tile0 = (int)tiles;
+        tiles += (long long)c.tiles_x * ((g.H + kChainTile - 1) / kChainTile);
+    }
+    if (tiles > 0x7fffffffLL || n_images > 65535) return dafne::fail(DAFNE_E_UNSUPPORTED, "corner_chain: grid too large");
+    hipLaunchKernelGGL(corner_chain_kernel, dim3((unsigned)tiles, n_images), dim3(256), 0, (hipStream_t)stream, D);
+    return dafne::check_launch("corner_chain");
 }
 
 }  // extern "C"

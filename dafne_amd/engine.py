@@ -66,6 +66,29 @@ class Pool:
 
 
 # --------------------------------------------------------------- weight packing
+RELEASED_HEAD = ("center-to-corner", True)     # (CORNER_PREDICTION, has centerness) of the released configs
+HEAD_STRATEGIES = ("center-to-corner", "direct", "offset", "iterative")
+
+
+def head_mode_of(sd, prefix="proposal_generator.dafne_head."):
+    """(CORNER_PREDICTION, has centerness) of a DAFNeHead state dict: each strategy has its own parameters (dafne.py:
+    212-247) -- center_pred (center-to-corner), c0_pred..c3_pred (iterative), base_corners (offset), none (direct)."""
+    if prefix + "center_pred.weight" in sd:
+        strategy = "center-to-corner"
+    elif prefix + "c0_pred.weight" in sd:
+        strategy = "iterative"
+    elif prefix + "base_corners" in sd:
+        strategy = "offset"
+    else:
+        strategy = "direct"
+    return strategy, prefix + "ctrness.weight" in sd
+
+
+def head_pred_channels(head_mode):
+    """Channels of the corners-tower prediction conv: 8 corner channels (+ ctrness)."""
+    return 9 if head_mode[1] else 8
+
+
 def pack_conv(weight, bias, device):
     """[Cout,Cin,KH,KW] fp32 (+bias) -> bf16 [Cout_pad, Cin/64, KH, KW, 64] flattened
     (k = 64-channel slab, kh, kw, channel in slab: the kernel walks the taps of one
@@ -965,22 +988,29 @@ _CAPTURE_MODE = "thread_local"
 
 class HeadOutputs:
     """Whole-batch head outputs shared by the sub-batch plans of a split batch; quacks like
-    a HeadPlan for dafne.head_levels()."""
+    a HeadPlan for dafne.head_levels().  head_mode: P["head_mode"] of the packed weights (which buffers the head has)."""
 
-    def __init__(self, n, h, w, num_classes, scales, device):
+    def __init__(self, n, h, w, num_classes, scales, device, head_mode=RELEASED_HEAD):
         p5 = (h // 32, w // 32)
         p6 = ((p5[0] + 1) // 2, (p5[1] + 1) // 2)             # 3x3 stride-2 pad-1 convs
         p7 = ((p6[0] + 1) // 2, (p6[1] + 1) // 2)
         sizes = [(h // 8, w // 8), (h // 16, w // 16), p5, p6, p7]
         f32 = torch.float32
+        strategy, has_ctr = head_mode
+        self.head_mode = head_mode
+        self.pred_c = head_pred_channels(head_mode)
         self.logits = [torch.empty(n, a, b, num_classes, dtype=f32, device=device) for a, b in sizes]
-        self.center = [torch.empty(n, a, b, 2, dtype=f32, device=device) for a, b in sizes]
-        self.delta_ctr = [torch.empty(n, a, b, 9, dtype=f32, device=device) for a, b in sizes]
+        self.center = ([torch.empty(n, a, b, 2, dtype=f32, device=device) for a, b in sizes]
+                       if strategy == "center-to-corner" else None)
+        self.delta_ctr = [torch.empty(n, a, b, self.pred_c, dtype=f32, device=device) for a, b in sizes]
+        self.corners = ([torch.empty(n, a, b, 8, dtype=f32, device=device) for a, b in sizes]
+                        if strategy == "iterative" else None)
         self.scales = scales
 
     def views(self, lo, hi):
-        return {"logits": [t[lo:hi] for t in self.logits], "center": [t[lo:hi] for t in self.center],
-                "delta_ctr": [t[lo:hi] for t in self.delta_ctr]}
+        return {k: [t[lo:hi] for t in v] for k, v in (("logits", self.logits), ("center", self.center),
+                                                     ("delta_ctr", self.delta_ctr), ("corners", self.corners))
+                if v is not None}
 
 
 class CallList:
@@ -998,17 +1028,26 @@ class CallList:
 
 class HeadPlan:
     """DAFNeHead over the 5 levels in single launches (weights are shared across
-    levels: dafne.py:350-494): 12 tower convs (+GroupNorm+ReLU) and 3 prediction
-    convs; outputs fp32 NHWC logits / [delta8|ctrness] / center."""
+    levels: dafne.py:350-494).  Released head (center-to-corner): 12 tower convs (+GroupNorm+ReLU) and 3 prediction
+    convs; outputs fp32 NHWC logits / [delta8|ctrness] / center.  Direct / offset / iterative heads (dafne.py:372-422):
+    8 tower convs (cls and corners towers, both on the FPN maps) and 2 prediction convs; outputs logits and
+    [corners8|ctrness] (offset: base_corners folded into the bias), for iterative [c0..c3 tower parts|ctrness] followed by
+    the corner chain (dafne_corner_chain_hip) into ``corners``.  Without centerness the prediction has 8 channels."""
 
     def __init__(self, P, feats, num_classes, device, pool, plan, outputs=None):
-        """outputs: optional {"logits"|"center"|"delta_ctr": [5 fp32 NHWC tensors]} to write
-        into (views of a larger batch's buffers when the batch is split over streams)."""
+        """outputs: optional {"logits"|"center"|"delta_ctr"|"corners": [5 fp32 NHWC tensors]} (the buffers the head mode
+        has, HeadOutputs.views) to write into (views of a larger batch's buffers when the batch is split over streams)."""
         L = _lib.load()
         n = feats[0].n
         self.levels = feats
         C = feats[0].c
         self.num_classes = num_classes
+        self.head_mode = P.get("head_mode", RELEASED_HEAD)
+        strategy, has_ctr = self.head_mode
+        stacked = strategy == "center-to-corner"       # corners tower on the center tower (CORNER_TOWER_ON_CENTER_TOWER)
+        pred_c = head_pred_channels(self.head_mode)
+        # the tower paired with cls_tower.i in one launch: the other FPN-fed tower
+        partner = "center_tower" if stacked else "corners_tower"
         calls = plan.calls
         sg = bool(getattr(plan, "shared_gpu", False))
         fuse_gn = os.environ.get("DAFNE_FUSE_GN", "1") != "0"
@@ -1021,7 +1060,7 @@ class HeadPlan:
         # against 1356-1365 img/s, two alternating runs; in round 3's in-phase layout the pairs cost 1-4 % there)
         pair_towers = os.environ.get("DAFNE_RP_PAIR", "1") != "0" and (not getattr(plan, "shared_gpu", False)
                                                                        or os.environ.get("DAFNE_RP_PAIR_SHARED", "1") == "1")
-        deferred = []              # intermediate maps of cls_tower / center_tower: released when BOTH towers are built (see below)
+        deferred = []              # intermediate maps of the paired towers: released when BOTH towers are built (see below)
 
         def tower(name, ins, in_gn, consumers):
             """4 x [conv3x3 -> GroupNorm(32) -> ReLU].  When the library's 3x3 patch kernel takes the layer
@@ -1119,29 +1158,34 @@ class HeadPlan:
                     nxt_gn = None
                 if i > 0:
                     for a in cur:
-                        # cls_tower.i and center_tower.i may run in ONE launch: a map the cls tower has released must not be
-                        # handed to the center tower while the pair that still reads it is in flight
-                        (deferred.append(a) if pair_towers and name != "corners_tower" else pool.put(a))
+                        # cls_tower.i and <partner>.i may run in ONE launch: a map the cls tower has released must not be
+                        # handed to the partner tower while the pair that still reads it is in flight (nor the other way)
+                        (deferred.append(a) if pair_towers and name in ("cls_tower", partner) else pool.put(a))
                 cur, cur_gn = outs, nxt_gn
             return cur, cur_gn
 
         fuse_pred = os.environ.get("DAFNE_FUSE_GN_PRED", "1") != "0"
         cls_t, cls_gn = tower("cls_tower", feats, None, [("cls_logits", num_classes, F_F32)] if fuse_pred else [])
-        ctr_t, ctr_gn = tower("center_tower", feats, None,
-                              [("center_pred", 2, F_F32), ("corners_tower.0", C, 0)] if fuse_pred else [])
-        for a in deferred:
-            pool.put(a)
-        cor_t, cor_gn = tower("corners_tower", ctr_t, ctr_gn, [("corners_ctrness", 9, F_F32)] if fuse_pred else [])
-        # cls_tower.i and center_tower.i are independent chains of identical shape: one launch of the persistent kernel for
-        # both (the pair takes cls_tower.i's place in the launch list: center_tower.i only moves EARLIER, behind the pair that
-        # holds center_tower.i-1 -- legal when that layer's statistics are finalised inside its kernel, F_GNFIN)
+        if stacked:
+            ctr_t, ctr_gn = tower("center_tower", feats, None,
+                                  [("center_pred", 2, F_F32), ("corners_tower.0", C, 0)] if fuse_pred else [])
+            for a in deferred:
+                pool.put(a)
+            cor_t, cor_gn = tower("corners_tower", ctr_t, ctr_gn, [("corners_ctrness", pred_c, F_F32)] if fuse_pred else [])
+        else:
+            cor_t, cor_gn = tower("corners_tower", feats, None, [("corners_ctrness", pred_c, F_F32)] if fuse_pred else [])
+            for a in deferred:
+                pool.put(a)
+        # cls_tower.i and <partner>.i are independent chains of identical shape: one launch of the persistent kernel for
+        # both (the pair takes cls_tower.i's place in the launch list: <partner>.i only moves EARLIER, behind the pair that
+        # holds <partner>.i-1 -- legal when that layer's statistics are finalised inside its kernel, F_GNFIN)
         if pair_towers:
             tagged = {c.tower_tag: c for c in calls if isinstance(c, ConvCall) and hasattr(c, "tower_tag")}
             for i in range(4):
-                a, b = tagged.get(("cls_tower", i)), tagged.get(("center_tower", i))
+                a, b = tagged.get(("cls_tower", i)), tagged.get((partner, i))
                 if a is None or b is None or a.wfrag is None or b.wfrag is None or a.prm.flags != b.prm.flags:
                     break
-                if i > 0 and not (tagged[("cls_tower", i - 1)].prm.flags & tagged[("center_tower", i - 1)].prm.flags & F_GNFIN):
+                if i > 0 and not (tagged[("cls_tower", i - 1)].prm.flags & tagged[(partner, i - 1)].prm.flags & F_GNFIN):
                     break
                 calls[calls.index(a)] = ConvPairCall(a, b)
                 calls.remove(b)
@@ -1160,8 +1204,21 @@ class HeadPlan:
             return outs
 
         self.logits = pred("cls_logits", cls_t, num_classes, "logits", cls_gn)
-        self.center = pred("center_pred", ctr_t, 2, "center", ctr_gn)
-        self.delta_ctr = pred("corners_ctrness", cor_t, 9, "delta_ctr", cor_gn)     # corners_pred (8) + ctrness (1) fused
+        self.center = pred("center_pred", ctr_t, 2, "center", ctr_gn) if stacked else None
+        # corners_pred (8) + ctrness (1) fused; iterative: the corners-tower parts of c0..c3_pred (8) + ctrness
+        self.delta_ctr = pred("corners_ctrness", cor_t, pred_c, "delta_ctr", cor_gn)
+        self.corners = None
+        if strategy == "iterative":
+            if outputs is not None:
+                self.corners = outputs["corners"]
+                assert all(o.is_contiguous() and tuple(o.shape) == (n, f.h, f.w, 8) for o, f in zip(self.corners, cor_t))
+            else:
+                self.corners = [torch.empty(n, f.h, f.w, 8, dtype=torch.float32, device=device) for f in cor_t]
+            segs = (_lib.ChainSeg * len(cor_t))()
+            for k, (t, o, f) in enumerate(zip(self.delta_ctr, self.corners, cor_t)):
+                segs[k] = _lib.ChainSeg(t.data_ptr(), o.data_ptr(), f.h, f.w)
+            calls.append(FnCall(L.dafne_corner_chain_hip, (segs, len(cor_t), n, pred_c, _lib.ptr(P["corner_chain"])),
+                                (segs, self.delta_ctr, self.corners, P["corner_chain"]), "corner_chain"))
         self.scales = P["scales"]
 
 
@@ -1209,12 +1266,25 @@ def pack_backbone_weights(sd, depth, device, prefix="backbone.", fp8=False):
 
 def pack_head_weights(sd, device, prefix="proposal_generator.dafne_head.", fp8=False):
     """DAFNeHead parameters -> packed weights.  corners_pred and ctrness both read
-    the corners tower (dafne.py:403,467-468) and are fused into one 9-channel conv.
+    the corners tower (dafne.py:403,467-468) and are fused into one 9-channel conv (8 without centerness).
+    Offset head: base_corners is folded into corners_pred's bias, so the base is added before the Scale as in the
+    reference (dafne.py:409-411), but inside the conv's fp32 bias addition: (conv + (bias + base)) instead of
+    ((conv + bias) + base) -- another rounding order, not another formula.
+    Iterative head: c{k}_pred reads cat(corners tower, c0..c{k-1}) (dafne.py:381-387); its weight is split into the
+    tower part (the first C input channels), which joins the fused prediction conv as channels 2k, 2k+1, and the
+    chain part, which goes to dafne_corner_chain_hip (P["corner_chain"], 216 fp32 weights).
     fp8: every weight is the dequantised e4m3 weight; the tower layers additionally get key + ".fp8" =
     (e4m3 bytes, scale) for the fp8 MFMA kernel (HeadPlan uses it where the input is normalised on load)."""
     P = {}
     hp = prefix
-    for tower in ("cls_tower", "center_tower", "corners_tower"):
+    mode = head_mode_of(sd, prefix)
+    strategy, has_ctr = mode
+    if fp8 and mode != RELEASED_HEAD:
+        raise NotImplementedError("ENGINE.WEIGHT_DTYPE fp8_e4m3 is calibrated for the released head only "
+                                  "(center-to-corner with centerness), got %s / centerness %s" % mode)
+    P["head_mode"] = mode
+    towers = ("cls_tower", "center_tower", "corners_tower") if strategy == "center-to-corner" else ("cls_tower", "corners_tower")
+    for tower in towers:
         for i in range(4):
             k = "%s%s.%d" % (hp, tower, 3 * i)
             P["%s.%d" % (tower, 3 * i)] = pack_conv(_wq(sd[k + ".weight"], fp8), sd[k + ".bias"], device)
@@ -1224,9 +1294,25 @@ def pack_head_weights(sd, device, prefix="proposal_generator.dafne_head.", fp8=F
             P["%s.%d.gn" % (tower, 3 * i + 1)] = (sd[g + ".weight"].float().to(device).contiguous(),
                                                   sd[g + ".bias"].float().to(device).contiguous())
     P["cls_logits"] = pack_conv(_wq(sd[hp + "cls_logits.weight"], fp8), sd[hp + "cls_logits.bias"], device)
-    P["center_pred"] = pack_conv(_wq(sd[hp + "center_pred.weight"], fp8), sd[hp + "center_pred.bias"], device)
-    wcc = torch.cat([sd[hp + "corners_pred.weight"].float(), sd[hp + "ctrness.weight"].float()], 0)
-    bcc = torch.cat([sd[hp + "corners_pred.bias"].float(), sd[hp + "ctrness.bias"].float()], 0)
+    if strategy == "center-to-corner":
+        P["center_pred"] = pack_conv(_wq(sd[hp + "center_pred.weight"], fp8), sd[hp + "center_pred.bias"], device)
+    if strategy == "iterative":
+        ws = [sd["%sc%d_pred.weight" % (hp, k)].float() for k in range(4)]
+        C = ws[0].shape[1]
+        wl = [w[:, :C] for w in ws]
+        bl = [sd["%sc%d_pred.bias" % (hp, k)].float() for k in range(4)]
+        P["corner_chain"] = torch.cat([w[:, C:].reshape(-1) for w in ws[1:]]).to(device).contiguous()
+        assert P["corner_chain"].numel() == 216
+    else:
+        wl = [sd[hp + "corners_pred.weight"].float()]
+        bl = [sd[hp + "corners_pred.bias"].float()]
+        if strategy == "offset":
+            bl = [bl[0] + sd[hp + "base_corners"].float().reshape(8)]
+    if has_ctr:
+        wl.append(sd[hp + "ctrness.weight"].float())
+        bl.append(sd[hp + "ctrness.bias"].float())
+    wcc = torch.cat(wl, 0) if len(wl) > 1 else wl[0]
+    bcc = torch.cat(bl, 0) if len(bl) > 1 else bl[0]
     P["corners_ctrness"] = pack_conv(_wq(wcc, fp8), bcc, device)
     P["scales"] = [float(sd["%sscales.%d.scale" % (hp, l)].reshape(-1)[0]) for l in range(5)]
     return P

@@ -1,10 +1,11 @@
 """`DAFNe` proposal generator and `DAFNeHead` for the MI355X engine.
 
 Same registry name, attributes and call contract as the reference
-(dafne/modeling/dafne/dafne.py:69-164 DAFNe, :167-494 DAFNeHead): the default
-center-to-corner branch with CORNER_TOWER_ON_CENTER_TOWER, CTR_ON_REG, GN towers
-and per-level Scale.  The ablation branches (direct / iterative / offset / angle,
-deformable convs, BN towers) are not built.
+(dafne/modeling/dafne/dafne.py:69-164 DAFNe, :167-494 DAFNeHead): CORNER_PREDICTION
+center-to-corner (the released head, CORNER_TOWER_ON_CENTER_TOWER), direct, offset and
+iterative, each with CENTERNESS oriented / plain / none, CTR_ON_REG, GN towers of 4
+convs and per-level Scale.  Not built: angle, MERGE_CORNER_CENTER_PRED, deformable
+convs, BN / no-norm towers, share convs.
 """
 import torch
 from torch import nn
@@ -24,39 +25,73 @@ def compute_locations(h, w, stride, device):
     return torch.stack((xx.reshape(-1), yy.reshape(-1)), dim=1) + stride // 2
 
 
+SUPPORTED_HEADS = ("CORNER_PREDICTION center-to-corner (CORNER_TOWER_ON_CENTER_TOWER, no MERGE_CORNER_CENTER_PRED), direct, "
+                   "offset or iterative; CENTERNESS oriented, plain or none; CTR_ON_REG, GN towers, 4+4 convs, no share "
+                   "convs, no deformable conv, USE_SCALE")
+
+
 class DAFNeHead(nn.Module):
     def __init__(self, cfg, input_shape):
         super().__init__()
         d = cfg.MODEL.DAFNE
-        if d.CORNER_PREDICTION != "center-to-corner" or d.MERGE_CORNER_CENTER_PRED \
-                or not d.CORNER_TOWER_ON_CENTER_TOWER or not d.CTR_ON_REG or d.NORM != "GN" \
+        strategy = d.CORNER_PREDICTION
+        c2c = strategy == "center-to-corner"
+        if strategy not in engine.HEAD_STRATEGIES or (c2c and (d.MERGE_CORNER_CENTER_PRED or not d.CORNER_TOWER_ON_CENTER_TOWER)) \
+                or not d.CTR_ON_REG or d.NORM != "GN" \
                 or d.USE_DEFORMABLE or d.NUM_SHARE_CONVS != 0 or not d.USE_SCALE \
-                or d.NUM_CLS_CONVS != 4 or d.NUM_BOX_CONVS != 4 or d.CENTERNESS == "none":
-            raise NotImplementedError("engine builds the released head: center-to-corner, stacked corner tower, "
-                                      "CTR_ON_REG, GN, 4+4 convs, USE_SCALE")
+                or d.NUM_CLS_CONVS != 4 or d.NUM_BOX_CONVS != 4 or d.CENTERNESS not in ("oriented", "plain", "none"):
+            raise NotImplementedError("engine builds %s (got CORNER_PREDICTION %r, CENTERNESS %r)"
+                                      % (SUPPORTED_HEADS, strategy, d.CENTERNESS))
+        self.corner_prediction_strategy = strategy
+        self.use_centerness = d.CENTERNESS != "none"
+        self.weight_dtype = cfg.ENGINE.WEIGHT_DTYPE       # bf16 | fp8_e4m3
+        if self.weight_dtype == "fp8_e4m3" and self.head_mode != engine.RELEASED_HEAD:
+            # the fp8 activation calibration names the released graph's FPN-fed layers (one_stage_detector.py:174)
+            raise NotImplementedError("ENGINE.WEIGHT_DTYPE fp8_e4m3 is built for the released head only (center-to-corner "
+                                      "with centerness), not CORNER_PREDICTION %r / CENTERNESS %r" % (strategy, d.CENTERNESS))
         chans = set(s.channels for s in input_shape)
         assert len(chans) == 1, "Each level must have the same channel!"
         c = chans.pop()
         self.num_classes = d.NUM_CLASSES
-        self.weight_dtype = cfg.ENGINE.WEIGHT_DTYPE       # bf16 | fp8_e4m3
         self.fpn_strides = d.FPN_STRIDES
         self.num_levels = len(input_shape)
         self.in_channels_to_top_module = c
+        # the reference's submodules of this mode, and only those (dafne.py:207-247, 286-302): same state-dict keys
         self.cls_tower = make_tower(c)
         self.corners_tower = make_tower(c)
         self.share_tower = nn.Sequential()
-        self.center_tower = make_tower(c)
+        if c2c:
+            self.center_tower = make_tower(c)
         self.cls_logits = ConvParams(self.num_classes, c, 3)
-        self.ctrness = ConvParams(1, c, 3)
-        self.corners_pred = ConvParams(8, c, 3)
-        self.center_pred = ConvParams(2, c, 3)
+        preds = [self.cls_logits]
+        if self.use_centerness:
+            self.ctrness = ConvParams(1, c, 3)
+            preds.append(self.ctrness)
+        if strategy in ("direct", "center-to-corner", "offset"):
+            self.corners_pred = ConvParams(8, c, 3)
+            preds.append(self.corners_pred)
+        if c2c:
+            self.center_pred = ConvParams(2, c, 3)
+            preds.append(self.center_pred)
+        if strategy == "offset":
+            self.base_corners = nn.Parameter(torch.tensor([-2.0, 2.0, 2.0, 2.0, 2.0, -2.0, -2.0, -2.0]).view(1, 8, 1, 1),
+                                             requires_grad=False)
+        if strategy == "iterative":
+            for k in range(4):
+                setattr(self, "c%d_pred" % k, ConvParams(2, c + 2 * k, 3))
+                preds.append(getattr(self, "c%d_pred" % k))
         self.scales = nn.ModuleList([ScaleParams(1.0) for _ in range(self.num_levels)])
-        for m in (self.cls_logits, self.ctrness, self.corners_pred, self.center_pred):
+        for m in preds:
             nn.init.normal_(m.weight, std=0.01)
             nn.init.constant_(m.bias, 0)
         nn.init.constant_(self.cls_logits.bias, cls_prior_bias(d.PRIOR_PROB))
         self._packed = None
         self._plans = {}
+
+    @property
+    def head_mode(self):
+        """(CORNER_PREDICTION, has centerness): engine.head_mode_of of this module's state dict."""
+        return self.corner_prediction_strategy, self.use_centerness
 
     def invalidate(self):
         self._packed = None
@@ -97,23 +132,37 @@ class DAFNeHead(nn.Module):
         for l in range(len(x)):
             sc = hp.scales[l]
             dc = hp.delta_ctr[l]
-            center = hp.center[l]
-            reg = (center.repeat(1, 1, 1, 4) + dc[..., :8]) * sc
+            if hp.center is not None:        # center-to-corner
+                center = hp.center[l]
+                reg = (center.repeat(1, 1, 1, 4) + dc[..., :8]) * sc
+                centers.append((center * sc).permute(0, 3, 1, 2).contiguous())
+            elif hp.corners is not None:     # iterative: cat(c0..c3) * s
+                reg = hp.corners[l] * sc
+            else:                            # direct: delta * s; offset: (base + delta) * s, base in the bias
+                reg = dc[..., :8] * sc
             logits.append(hp.logits[l].permute(0, 3, 1, 2).contiguous())
             regs.append(reg.permute(0, 3, 1, 2).contiguous())
-            centers.append((center * sc).permute(0, 3, 1, 2).contiguous())
-            ctrs.append(dc[..., 8:9].permute(0, 3, 1, 2).contiguous())
+            if self.use_centerness:
+                ctrs.append(dc[..., 8:9].permute(0, 3, 1, 2).contiguous())
+            else:                            # dafne.py:474-480
+                ctrs.append(torch.ones(dc.shape[0], 1, dc.shape[1], dc.shape[2], dtype=dc.dtype, device=dc.device))
         return logits, regs, centers, [], ctrs, [], {"corners_towers": [], "center_towers": [], "cls_towers": []}
 
 
 def head_levels(hp, strides):
     """HeadPlan outputs -> decode inputs (no copies: strided views into the fused
-    [delta8|ctrness] buffer)."""
+    [delta8|ctrness] buffer).  Heads without center_pred decode delta as the whole regression (center None), the
+    iterative head its chain output; without centerness ctrness is None (score = sigmoid(cls))."""
     levels = []
     for l, s in enumerate(strides):
         dc = hp.delta_ctr[l]
-        levels.append(pp.LevelInput(hp.logits[l], dc, hp.center[l], dc.view(-1)[8:], s, hp.scales[l],
-                                    delta_ps=9, center_ps=2, ctrness_ps=9))
+        pc = dc.shape[-1]
+        ctr = dc.view(-1)[8:] if pc == 9 else None
+        center = hp.center[l] if hp.center is not None else None
+        corners = getattr(hp, "corners", None)
+        delta, dps = (corners[l], 8) if corners is not None else (dc, pc)
+        levels.append(pp.LevelInput(hp.logits[l], delta, center, ctr, s, hp.scales[l],
+                                    delta_ps=dps, center_ps=2, ctrness_ps=pc))
     return levels
 
 

@@ -30,8 +30,6 @@ class DAFNeOutputs(nn.Module):
         self.centerness_mode = d.CENTERNESS
         self.has_centerness = self.centerness_mode != "none"
         assert self.centerness_mode in ["none", "plain", "oriented"]
-        if not self.has_centerness:
-            raise NotImplementedError("CENTERNESS='none' is not used by any released config")
         self.corner_prediction_strategy = d.CORNER_PREDICTION
         self.num_classes = d.NUM_CLASSES
         self.strides = d.FPN_STRIDES
@@ -87,12 +85,11 @@ class DAFNeOutputs(nn.Module):
         accepted for signature parity; the kernel regenerates them (dafne.py:37-44)."""
         levels = []
         for lg, rc, ct, s in zip(logits_pred, corners_reg_pred, ctrness_pred, self.strides):
-            n, _, h, w = lg.shape
             lg_n = lg.detach().float().permute(0, 2, 3, 1).contiguous()
             rc_n = rc.detach().float().permute(0, 2, 3, 1).contiguous()
-            ct_n = ct.detach().float().permute(0, 2, 3, 1).contiguous()
-            zero = torch.zeros(n, h, w, 2, dtype=torch.float32, device=lg.device)
-            levels.append(pp.LevelInput(lg_n, rc_n, zero, ct_n, s, 1.0))
+            # CENTERNESS none: the head's dummy ones are not read (dafne_outputs.py:810-830, score = sigmoid(cls))
+            ct_n = ct.detach().float().permute(0, 2, 3, 1).contiguous() if self.has_centerness else None
+            levels.append(pp.LevelInput(lg_n, rc_n, None, ct_n, s, 1.0))
         rows, counts = self.predict_packed(levels)
         sizes = [tuple(int(v) for v in (s.tolist() if isinstance(s, torch.Tensor) else s)) for s in image_sizes]
         return pp.rows_to_instances(rows, counts, sizes)

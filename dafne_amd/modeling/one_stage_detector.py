@@ -375,9 +375,13 @@ class OneStageDetector(nn.Module):
                 self._last_head = plan.head          # (tests: the head outputs the returned detections were decoded from)
                 if getattr(self.cfg.ENGINE, "CHECK_FINITE", False):
                     # the FPN maps first: behind them GroupNorm-on-load computes max(a x + b, 0), which turns a NaN into 0 again
-                    for l, (ft, lg, dc, ce) in enumerate(zip(plan.features, plan.head.logits, plan.head.delta_ctr, plan.head.center)):
-                        for nme, t in (("FPN map", ft.t), ("logits", lg), ("delta / ctrness", dc), ("center", ce)):
-                            if not bool(torch.isfinite(t).all()):
+                    hd = plan.head
+                    for l, ft in enumerate(plan.features):
+                        # the buffers of the head's mode: no center without center_pred, chain output of the iterative head
+                        for nme, t in (("FPN map", ft.t), ("logits", hd.logits[l]), ("delta / ctrness", hd.delta_ctr[l]),
+                                       ("center", hd.center[l] if hd.center is not None else None),
+                                       ("corners", hd.corners[l] if hd.corners is not None else None)):
+                            if t is not None and not bool(torch.isfinite(t).all()):
                                 raise _lib.DafneHipError("ENGINE.CHECK_FINITE: non-finite %s at level %d (weights / input overflow? a NaN "
                                                          "accumulator of a non-ReLU layer turns into -inf)" % (nme, l))
                 return outs.predict_packed(head_levels(plan.head, strides), sizes=sizes,
@@ -403,7 +407,8 @@ class OneStageDetector(nn.Module):
                 # set is reusable only when its post-process has finished, which starts at the NEXT call's head towers
                 nsets = 2 if splits > 1 else max(2, int(os.environ.get("DAFNE_B1_SETS", "4")))
                 for _ in range(nsets):
-                    ho = engine.HeadOutputs(n, hn, wn, nc, self._weights()["scales"], self.device)
+                    ho = engine.HeadOutputs(n, hn, wn, nc, self._weights()["scales"], self.device,
+                                            head_mode=self._weights()["head_mode"])
                     hos.append(ho)
                     plan_sets.append([engine.DensePlan(self._weights(), bounds[k + 1] - bounds[k], hn, wn, self.depth,
                                                        nc, self.device, head_outputs=ho.views(bounds[k], bounds[k + 1]),

@@ -15,7 +15,9 @@ from .structures import Boxes, Instances
 
 
 class LevelInput:
-    """One FPN level's raw head outputs in NHWC fp32 (device)."""
+    """One FPN level's raw head outputs in NHWC fp32 (device).  ``center`` is None for the heads without a center
+    regression (direct / offset / iterative: ``delta`` is then the whole corner regression), ``ctrness`` None for
+    CENTERNESS none (score = sigmoid(cls))."""
 
     def __init__(self, logits, delta, center, ctrness, stride, scale=1.0,
                  delta_ps=None, center_ps=None, ctrness_ps=None, logits_ps=None):
@@ -45,21 +47,30 @@ class Candidates:
         self.counts = torch.zeros(n, dtype=i32, device=device)
 
 
+def decode_flags(levels):
+    """dafne_decode_params.flags for these levels: every level must agree on which inputs it has."""
+    no_center = set(lv.center is None for lv in levels)
+    no_ctr = set(lv.ctrness is None for lv in levels)
+    assert len(no_center) == 1 and len(no_ctr) == 1, "levels disagree on center / ctrness"
+    return (_lib.DECODE_NO_CENTER if no_center.pop() else 0) | (_lib.DECODE_NO_CTRNESS if no_ctr.pop() else 0)
+
+
 def decode_levels(levels, *, num_classes, pre_nms_thresh, pre_nms_topk, thresh_with_ctr,
-                  sort_corners, out=None):
-    """forward_for_single_feature_map over all levels/images -> Candidates."""
+                  sort_corners, out=None, flags=None):
+    """forward_for_single_feature_map over all levels/images -> Candidates.  flags: None = from the levels' inputs
+    (decode_flags); an explicit value is passed to the library as it is."""
     L = _lib.load()
     dev = levels[0].logits.device
     n = levels[0].N
     prm = _lib.DecodeParams(n, len(levels), num_classes, pre_nms_topk, float(pre_nms_thresh),
                             int(bool(thresh_with_ctr)), int(bool(sort_corners)),
-                            len(levels) * pre_nms_topk)
+                            len(levels) * pre_nms_topk, decode_flags(levels) if flags is None else int(flags))
     descs = (_lib.LevelDesc * len(levels))()
     for i, lv in enumerate(levels):
         for t in (lv.logits, lv.delta, lv.center, lv.ctrness):
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-        descs[i] = _lib.LevelDesc(lv.logits.data_ptr(), lv.delta.data_ptr(), lv.center.data_ptr(),
-                                  lv.ctrness.data_ptr(), lv.logits_ps, lv.delta_ps, lv.center_ps,
+            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous())
+        descs[i] = _lib.LevelDesc(lv.logits.data_ptr(), lv.delta.data_ptr(), _lib.ptr(lv.center),
+                                  _lib.ptr(lv.ctrness), lv.logits_ps, lv.delta_ps, lv.center_ps,
                                   lv.ctrness_ps, lv.H, lv.W, lv.stride, lv.scale)
     with torch.cuda.device(dev):
         cand = out if out is not None else Candidates(n, prm.m_cap, dev)

@@ -147,12 +147,21 @@ typedef struct dafne_decode_params {
     int32_t thresh_with_ctr;  /* THRESH_WITH_CTR                        */
     int32_t sort_corners;     /* SORT_CORNERS                           */
     int32_t m_cap;            /* rows per image in the outputs (>= n_levels*pre_nms_topk) */
+    int32_t flags;            /* 0 (released head) or DAFNE_DECODE_* bits below; unknown bits are rejected */
 } dafne_decode_params;
+
+/* Heads without a center regression (CORNER_PREDICTION direct / offset / iterative, dafne.py:372-422): corners =
+ * delta*scale*stride + location; d_center may be NULL. */
+#define DAFNE_DECODE_NO_CENTER 1
+/* CENTERNESS none (dafne.py:474-480, dafne_outputs.py:810-830): score = sigmoid(cls), no square root, centerness
+ * reported as 1.0, thresh_with_ctr ignored; d_ctrness may be NULL. */
+#define DAFNE_DECODE_NO_CTRNESS 2
 
 /*
  * forward_for_single_feature_map for every level and image
  * (dafne_outputs.py:771-772,792-905): sigmoid, sqrt(cls*ctr), threshold, per
- * level top-k, corner decode ((center.repeat+delta)*scale*stride + location),
+ * level top-k, corner decode ((center.repeat+delta)*scale*stride + location;
+ * delta*scale*stride + location with DAFNE_DECODE_NO_CENTER),
  * optional canonical corner order, hull box.  Outputs are per image, levels
  * concatenated in order, candidates within a level in (location, class) order:
  *   d_corners [N, m_cap, 8], d_scores [N, m_cap], d_ctr [N, m_cap],
@@ -517,6 +526,21 @@ int dafne_groupnorm_relu_nhwc_bf16_hip(const dafne_gn_seg* segs, int n_segs, int
                                        const float* d_beta, float eps, void* stream);
 /* out = relu(in) on n_elems bf16 values (n_elems % 8 == 0); halo zeros stay zero. */
 int dafne_relu_copy_bf16_hip(const void* d_in, void* d_out, int64_t n_elems, void* stream);
+
+/* ------------------------------------------------ iterative corner chain */
+typedef struct dafne_chain_seg {
+    const float* d_t;   /* [N, H, W, t_ps] fp32: channels 2k, 2k+1 = c{k}_pred's corners-tower part + bias (k = 0..3) */
+    float* d_out;       /* [N, H, W, 8] fp32: [c0|c1|c2|c3]; must not alias d_t (halo pixels of d_t are re-read) */
+    int32_t H, W;
+} dafne_chain_seg;
+/*
+ * CORNER_PREDICTION iterative (dafne.py:381-387) after its tower parts: c0 = T[0:2], c_k = T[2k:2k+2] +
+ * conv3x3(cat(c0..c_{k-1}); W_k) with zero padding at the map border, k = 1..3, in fp32, one launch for every
+ * segment (level) and image.  d_w: the 216 chain weights, c1_pred.weight[:, C:], c2_pred.weight[:, C:],
+ * c3_pred.weight[:, C:] (OIHW fp32, 36 + 72 + 108 floats).  n_segs <= 8, t_ps >= 8.
+ */
+int dafne_corner_chain_hip(const dafne_chain_seg* segs, int n_segs, int n_images, int t_ps, const float* d_w,
+                           void* stream);
 
 #ifdef __cplusplus
 }
