@@ -36,6 +36,11 @@ class DecodeParams(ctypes.Structure):
 DECODE_NO_CENTER, DECODE_NO_CTRNESS = 1, 2       # dafne_decode_params.flags (include/dafne_amd.h)
 
 
+class SceneTile(ctypes.Structure):
+    _fields_ = [("d_scene", c_void_p), ("h", c_i32), ("w", c_i32), ("layout_hwc", c_i32), ("left", c_i32), ("up", c_i32),
+                ("reserved", c_i32)]
+
+
 class ChainSeg(ctypes.Structure):
     _fields_ = [("d_t", c_void_p), ("d_out", c_void_p), ("H", c_i32), ("W", c_i32)]
 
@@ -132,6 +137,11 @@ SIGNATURES = {
     "dafne_groupnorm_relu_nhwc_bf16_hip": (c_int, [ctypes.POINTER(GnSeg), c_int, c_int, c_int, c_void_p, c_void_p,
                                                    c_void_p, c_void_p, c_float, c_void_p]),
     "dafne_relu_copy_bf16_hip": (c_int, [c_void_p, c_void_p, c_i64, c_void_p]),
+    "dafne_scene_tiles_workspace_bytes": (c_size_t, [c_int]),
+    "dafne_scene_tiles_u8_hip": (c_int, [ctypes.POINTER(SceneTile), c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dafne_scene_merge_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dafne_scene_merge_rows_hip": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_uint64, c_int,
+                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

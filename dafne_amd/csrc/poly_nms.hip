@@ -1885,3 +1885,165 @@ int dafne_select_over_all_levels_hip(const float* d_boxes8, const float* d_score
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------- whole-scene merge rows
+// The tile merge after the Task1 text round trip (dota_evaluation._generate_task_1_files writes "%s %.4f %.2f .. %.2f",
+// ResultMerge_multi_process.mergebypoly parses the lines back and shifts them into the scene with poly2origpoly) as the fp64
+// rows dafne_poly_nms_f64_batched_hip takes, bit for bit what the text route parses:
+//   coordinate q = rint(double(v) * 100) / 100   == float("%.2f" % v)   (the product is exact, rint rounds half to even,
+//   score      q = rint(double(v) * 1e4) / 1e4   == float("%.4f" % v)    the division is correctly rounded)
+// then (q + left | up) / 1.0.  One bucket per (scene, class), in tile order and then the tile's row order: a count, an ordered
+// scan and ballot ranks -- no atomic decides a position.  (This unit is built with -ffp-contract=off.)
+namespace {
+
+constexpr int kMaxClasses = 64;
+constexpr int kMergeThreads = 256;
+
+__device__ __forceinline__ int row_label(const float* row, int n_classes, unsigned long long skip) {
+    const float f = row[10];
+    if (!(f >= 0.0f) || f >= (float)n_classes) return -1;
+    const int c = (int)f;
+    return ((skip >> c) & 1ull) ? -1 : c;
+}
+
+// hist[t][c]: rows of tile t that go to class bucket c
+__global__ void __launch_bounds__(kMergeThreads) merge_hist_kernel(const float* __restrict__ rows, const int32_t* __restrict__ counts,
+                                                                   int k_cap, int n_classes, unsigned long long skip,
+                                                                   int32_t* __restrict__ hist) {
+    __shared__ int h[kMaxClasses];
+    const int t = blockIdx.x;
+    if (threadIdx.x < kMaxClasses) h[threadIdx.x] = 0;
+    __syncthreads();
+    int n = counts[t];
+    n = n < 0 ? 0 : (n > k_cap ? k_cap : n);
+    for (int r = threadIdx.x; r < n; r += blockDim.x) {
+        const int c = row_label(rows + ((size_t)t * k_cap + r) * DAFNE_DET_ROW, n_classes, skip);
+        if (c >= 0) atomicAdd(&h[c], 1);           // a count only: positions come from the ordered scan below
+    }
+    __syncthreads();
+    if (threadIdx.x < n_classes) hist[(size_t)t * n_classes + threadIdx.x] = h[threadIdx.x];
+}
+
+// one thread per (scene, class) bucket: offs[t][c] = rows of the same bucket in the tiles before t, in tile order
+__global__ void __launch_bounds__(256) merge_scan_kernel(const int32_t* __restrict__ hist, const int32_t* __restrict__ tile_info,
+                                                         int n_tiles, int n_scenes, int n_classes, int32_t* __restrict__ offs,
+                                                         int32_t* __restrict__ bucket_counts) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_scenes * n_classes) return;
+    const int s = b / n_classes, c = b - s * n_classes;
+    int run = 0;
+    for (int t = 0; t < n_tiles; t++) {
+        if (tile_info[3 * t + 2] != s) continue;
+        offs[(size_t)t * n_classes + c] = run;
+        run += hist[(size_t)t * n_classes + c];
+    }
+    bucket_counts[b] = run;
+}
+
+__device__ __forceinline__ double quantise(float v, double scale) {
+    return rint((double)v * scale) / scale;
+}
+
+// one block per tile: stable per-class rank of every row (wave ballots, waves in order, chunks in order), then the row
+__global__ void __launch_bounds__(kMergeThreads) merge_write_kernel(const float* __restrict__ rows, const int32_t* __restrict__ counts,
+                                                                    int k_cap, const int32_t* __restrict__ tile_info, int n_scenes,
+                                                                    int n_classes,
+                                                                    unsigned long long skip, int score_mode,
+                                                                    const int32_t* __restrict__ offs, int m_cap,
+                                                                    double* __restrict__ dets, int32_t* __restrict__ src) {
+    constexpr int kWaves = kMergeThreads / 64;
+    __shared__ int base[kMaxClasses];
+    __shared__ int wcnt[kWaves][kMaxClasses];
+    const int t = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int left = tile_info[3 * t], up = tile_info[3 * t + 1], s = tile_info[3 * t + 2];
+    if (s < 0 || s >= n_scenes) return;                // (block-uniform) a tile of no scene of this call has no bucket
+    if (threadIdx.x < n_classes) base[threadIdx.x] = offs[(size_t)t * n_classes + threadIdx.x];
+    int n = counts[t];
+    n = n < 0 ? 0 : (n > k_cap ? k_cap : n);
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (int r0 = 0; r0 < n; r0 += kMergeThreads) {
+        for (int k = threadIdx.x; k < kWaves * kMaxClasses; k += kMergeThreads) (&wcnt[0][0])[k] = 0;
+        __syncthreads();
+        const int r = r0 + threadIdx.x;
+        const float* row = rows + ((size_t)t * k_cap + (r < n ? r : 0)) * DAFNE_DET_ROW;
+        const int c = r < n ? row_label(row, n_classes, skip) : -1;
+        // lanes of this wave with the same class: six label-bit ballots
+        unsigned long long peers = __ballot(c >= 0);
+#pragma unroll
+        for (int bit = 0; bit < 6; bit++) {
+            const unsigned long long m = __ballot(c >= 0 && ((c >> bit) & 1));
+            peers &= ((c >> bit) & 1) ? m : ~m;
+        }
+        if (c >= 0 && (peers & lt) == 0) wcnt[wave][c] = __popcll(peers);
+        __syncthreads();
+        if (c >= 0) {
+            int pos = base[c] + __popcll(peers & lt);
+            for (int w = 0; w < wave; w++) pos += wcnt[w][c];
+            if (pos < m_cap) {
+                const size_t o = (size_t)s * n_classes + c;
+                double* d = dets + (o * m_cap + pos) * 9;
+#pragma unroll
+                for (int k = 0; k < 8; k++) d[k] = (quantise(row[k], 100.0) + (double)((k & 1) ? up : left)) / 1.0;
+                float v = row[8];
+                if (score_mode) {
+                    const float sq = v * v;
+                    v = sq / row[9];
+                }
+                d[8] = quantise(v, 10000.0);
+                src[o * m_cap + pos] = t * k_cap + r;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < n_classes) {
+            int add = 0;
+            for (int w = 0; w < kWaves; w++) add += wcnt[w][threadIdx.x];
+            base[threadIdx.x] += add;
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dafne_scene_merge_workspace_bytes(int n_tiles, int n_classes) {
+    if (n_tiles < 1 || n_classes < 1 || n_classes > kMaxClasses) return 0;
+    return 2 * dafne::align_up(sizeof(int32_t) * (size_t)n_tiles * n_classes, 256);
+}
+
+int dafne_scene_merge_rows_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap, const int32_t* d_tile_info,
+                               int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap, double* d_dets,
+                               int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!d_rows || !d_counts || !d_tile_info || !d_bucket_counts || !d_ws || n_tiles < 1 || k_cap < 1 || n_scenes < 1 ||
+        m_cap < 0 || (score_mode != 0 && score_mode != 1))
+        return dafne::fail(DAFNE_E_INVALID, "scene_merge_rows: bad args (n_tiles %d, k_cap %d, n_scenes %d, m_cap %d, score_mode %d)",
+                           n_tiles, k_cap, n_scenes, m_cap, score_mode);
+    if (n_classes < 1 || n_classes > kMaxClasses)
+        return dafne::fail(DAFNE_E_INVALID, "scene_merge_rows: n_classes %d not in [1, %d]", n_classes, kMaxClasses);
+    if (m_cap > 0 && (!d_dets || !d_src)) return dafne::fail(DAFNE_E_INVALID, "scene_merge_rows: m_cap %d without d_dets / d_src", m_cap);
+    if ((size_t)n_tiles * k_cap > (size_t)INT32_MAX)
+        return dafne::fail(DAFNE_E_UNSUPPORTED, "scene_merge_rows: %d tiles x %d rows overflow the int32 back-index", n_tiles, k_cap);
+    if (ws_bytes < dafne_scene_merge_workspace_bytes(n_tiles, n_classes))
+        return dafne::fail(DAFNE_E_WORKSPACE, "scene_merge_rows: workspace %zu < %zu", ws_bytes,
+                           dafne_scene_merge_workspace_bytes(n_tiles, n_classes));
+    hipStream_t st = (hipStream_t)stream;
+    dafne::WsCarver c(d_ws);
+    int32_t* hist = c.take<int32_t>((size_t)n_tiles * n_classes);
+    int32_t* offs = c.take<int32_t>((size_t)n_tiles * n_classes);
+    hipLaunchKernelGGL(merge_hist_kernel, dim3(n_tiles), dim3(kMergeThreads), 0, st, d_rows, d_counts, k_cap, n_classes,
+                       (unsigned long long)skip_mask, hist);
+    int rc = dafne::check_launch("scene_merge_hist");
+    if (rc) return rc;
+    const int nb = n_scenes * n_classes;
+    hipLaunchKernelGGL(merge_scan_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, hist, d_tile_info, n_tiles, n_scenes, n_classes,
+                       offs, d_bucket_counts);
+    rc = dafne::check_launch("scene_merge_scan");
+    if (rc || m_cap == 0) return rc;
+    hipLaunchKernelGGL(merge_write_kernel, dim3(n_tiles), dim3(kMergeThreads), 0, st, d_rows, d_counts, k_cap, d_tile_info,
+                       n_scenes, n_classes, (unsigned long long)skip_mask, score_mode, offs, m_cap, d_dets, d_src);
+    return dafne::check_launch("scene_merge_write");
+}
+
+}  // extern "C"

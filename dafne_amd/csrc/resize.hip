@@ -123,3 +123,120 @@ int dafne_resize_bilinear_u8_hip(const uint8_t* d_in, int layout_hwc, int C, int
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- whole-scene tile gather
+// The DOTA split (tools/prepare_dota SplitOnlyImage_multi_process.SplitSingle, saveimagepatches(padding=True)) as one launch
+// over every tile of every scene of a call: tile t is the patch x patch crop of its scene at (left, up), zero past the edge.
+namespace {
+
+constexpr int kPix = 8;        // pixels per thread of the tile gather: 24 output bytes, three 8-byte stores
+
+// 4-byte-aligned word that holds byte p; every word read holds at least one byte of the source row, so no read leaves
+// the allocation's last word
+__device__ __forceinline__ uint32_t word_at(const uint8_t* base, size_t p) {
+    return *reinterpret_cast<const uint32_t*>(base + (p & ~(size_t)3));
+}
+
+// n bytes (n % 4 == 0, n <= 24) starting at the unaligned byte offset p, as n / 4 little-endian words
+template <int N>
+__device__ __forceinline__ void load_unaligned(const uint8_t* base, size_t p, uint32_t (&out)[N]) {
+    const int sh = (int)(p & 3) * 8;
+    uint32_t w[N + 1];
+#pragma unroll
+    for (int k = 0; k < N; k++) w[k] = word_at(base, p + 4 * k);
+    w[N] = sh ? word_at(base, p + 4 * N) : 0u;       // only when the span crosses one more word
+#pragma unroll
+    for (int k = 0; k < N; k++) out[k] = sh ? (uint32_t)((((uint64_t)w[k + 1]) << 32 | w[k]) >> sh) : w[k];
+}
+
+// One thread = 8 consecutive output pixels of one tile row.  Interior: aligned word loads + shifts, three 8-byte
+// stores.  Edge (any of the 8 pixels past the scene): byte loads under a mask, zeros outside.
+__global__ void __launch_bounds__(256) scene_tiles_kernel(const dafne_scene_tile* __restrict__ tiles, int n_tiles, int patch,
+                                                          uint8_t* __restrict__ out) {
+    const int per_row = patch / kPix;
+    const size_t per_tile = (size_t)patch * per_row;
+    const size_t total = per_tile * n_tiles;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int t = (int)(i / per_tile);
+        const size_t r = i - (size_t)t * per_tile;
+        const int y = (int)(r / per_row);
+        const int x0 = (int)(r - (size_t)y * per_row) * kPix;
+        const dafne_scene_tile d = tiles[t];
+        const int sy = d.up + y, sx = d.left + x0;
+        uint32_t o[6];
+        if (sy < d.h && sx + kPix <= d.w) {
+            if (d.layout_hwc) {
+                load_unaligned<6>(d.d_scene, ((size_t)sy * d.w + sx) * 3, o);
+            } else {
+                const size_t plane = (size_t)d.h * d.w;
+                const size_t p = (size_t)sy * d.w + sx;
+                uint32_t c[3][2];
+                load_unaligned<2>(d.d_scene, p, c[0]);
+                load_unaligned<2>(d.d_scene + plane, p, c[1]);
+                load_unaligned<2>(d.d_scene + 2 * plane, p, c[2]);
+                uint8_t b[24];
+#pragma unroll
+                for (int k = 0; k < kPix; k++)
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) b[3 * k + ch] = (uint8_t)(c[ch][k >> 2] >> (8 * (k & 3)));
+#pragma unroll
+                for (int k = 0; k < 6; k++)
+                    o[k] = (uint32_t)b[4 * k] | (uint32_t)b[4 * k + 1] << 8 | (uint32_t)b[4 * k + 2] << 16 |
+                           (uint32_t)b[4 * k + 3] << 24;
+            }
+        } else {
+            uint8_t b[24];
+            const size_t plane = (size_t)d.h * d.w;
+#pragma unroll
+            for (int k = 0; k < kPix; k++) {
+                const bool in = sy < d.h && sx + k < d.w;
+                const size_t p = in ? (size_t)sy * d.w + sx + k : 0;
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++)
+                    b[3 * k + ch] = in ? (d.layout_hwc ? d.d_scene[p * 3 + ch] : d.d_scene[ch * plane + p]) : (uint8_t)0;
+            }
+#pragma unroll
+            for (int k = 0; k < 6; k++)
+                o[k] = (uint32_t)b[4 * k] | (uint32_t)b[4 * k + 1] << 8 | (uint32_t)b[4 * k + 2] << 16 | (uint32_t)b[4 * k + 3] << 24;
+        }
+        // byte offset ((t * patch + y) * patch + x0) * 3 is a multiple of 24: 8-byte aligned
+        uint2* dst = reinterpret_cast<uint2*>(out + (((size_t)t * patch + y) * patch + x0) * 3);
+        dst[0] = make_uint2(o[0], o[1]);
+        dst[1] = make_uint2(o[2], o[3]);
+        dst[2] = make_uint2(o[4], o[5]);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dafne_scene_tiles_workspace_bytes(int n_tiles) {
+    if (n_tiles < 1) return 0;
+    return dafne::align_up(sizeof(dafne_scene_tile) * (size_t)n_tiles, 256);
+}
+
+int dafne_scene_tiles_u8_hip(const dafne_scene_tile* tiles, int n_tiles, int patch, uint8_t* d_out_hwc, void* d_ws,
+                             size_t ws_bytes, void* stream) {
+    if (!tiles || !d_out_hwc || !d_ws || n_tiles < 1 || patch < kPix)
+        return dafne::fail(DAFNE_E_INVALID, "scene_tiles: bad args (n_tiles %d, patch %d)", n_tiles, patch);
+    if (patch % kPix) return dafne::fail(DAFNE_E_UNSUPPORTED, "scene_tiles: patch %d is not a multiple of %d", patch, kPix);
+    if (ws_bytes < dafne_scene_tiles_workspace_bytes(n_tiles))
+        return dafne::fail(DAFNE_E_WORKSPACE, "scene_tiles: workspace %zu < %zu", ws_bytes, dafne_scene_tiles_workspace_bytes(n_tiles));
+    for (int t = 0; t < n_tiles; t++) {
+        const dafne_scene_tile& d = tiles[t];
+        if (!d.d_scene || d.h < 1 || d.w < 1 || (d.layout_hwc != 0 && d.layout_hwc != 1) || d.left < 0 || d.up < 0 ||
+            d.left >= d.w || d.up >= d.h)
+            return dafne::fail(DAFNE_E_INVALID, "scene_tiles: tile %d: scene %dx%d layout %d origin (%d, %d)", t, d.h, d.w,
+                               d.layout_hwc, d.left, d.up);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    DAFNE_HIP_TRY(hipMemcpyAsync(d_ws, tiles, sizeof(dafne_scene_tile) * (size_t)n_tiles, hipMemcpyHostToDevice, st));
+    const size_t total = (size_t)n_tiles * patch * (patch / kPix);
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(scene_tiles_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st,
+                       (const dafne_scene_tile*)d_ws, n_tiles, patch, d_out_hwc);
+    return dafne::check_launch("scene_tiles");
+}
+
+}  // extern "C"

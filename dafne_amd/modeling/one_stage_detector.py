@@ -552,6 +552,15 @@ class OneStageDetector(nn.Module):
                 t.record_stream(main)
             return res
 
+    def detect_scenes(self, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None):
+        """Whole scenes in, scene-coordinate detections out: the reference's split_dota.py (rate 1) + tile inference + the tile
+        merge (mergebypoly) in one call, on the device (dafne_amd/scene.py).  scenes: device uint8 BGR [H,W,3] or [3,H,W]
+        images.  -> one dict per scene: corners [K,8] f64, scores [K] f64 (the merge's 4-decimal values), labels [K], tile /
+        row (the tile row each detection came from), origins (the scene's tile origins); class by class, each in NMS keep
+        order.  scene.write_task1_merged writes them as Task1_merged/ files."""
+        from .. import scene
+        return scene.detect_scenes(self, scenes, patch_size=patch_size, overlap=overlap, batch=batch, layout_hwc=layout_hwc)
+
     @staticmethod
     def _enqueue_eager(plans, cs, sp, splits, defer):
         """Launch j of every sub-batch before launch j + 1; defer: an event per stream where its head begins."""

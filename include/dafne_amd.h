@@ -542,6 +542,41 @@ typedef struct dafne_chain_seg {
 int dafne_corner_chain_hip(const dafne_chain_seg* segs, int n_segs, int n_images, int t_ps, const float* d_w,
                            void* stream);
 
+/* ------------------------------------------------------ whole-scene inference */
+/*
+ * The DOTA split in one launch (tools/prepare_dota SplitOnlyImage_multi_process.SplitSingle at rate 1,
+ * saveimagepatches(padding=True)): tile t is the patch x patch crop of its scene at (left, up), pixels past the
+ * scene edge 0.  `tiles` is a HOST array of n_tiles descriptors (checked on the host, copied into d_ws on `stream`);
+ * d_scene: uint8 BGR [H,W,3] (layout_hwc = 1) or [3,H,W] (= 0), 0 <= left < w, 0 <= up < h.  d_out_hwc: [n_tiles,
+ * patch, patch, 3] uint8, 8-byte aligned (detect_packed(layout_hwc=True) takes it).  patch % 8 != 0 ->
+ * DAFNE_E_UNSUPPORTED.  d_ws: dafne_scene_tiles_workspace_bytes(n_tiles) bytes.
+ */
+typedef struct dafne_scene_tile {
+    const uint8_t* d_scene;
+    int32_t h, w, layout_hwc, left, up, reserved;
+} dafne_scene_tile;
+size_t dafne_scene_tiles_workspace_bytes(int n_tiles);
+int dafne_scene_tiles_u8_hip(const dafne_scene_tile* tiles, int n_tiles, int patch, uint8_t* d_out_hwc, void* d_ws,
+                             size_t ws_bytes, void* stream);
+/*
+ * Tile detections -> the f64 rows of the tile merge (ResultMerge_multi_process.mergebypoly after
+ * _generate_task_1_files' text round trip), one bucket per (scene, class): bucket s * n_classes + c.
+ *   d_rows [n_tiles, k_cap, DAFNE_DET_ROW] f32 + d_counts [n_tiles] (detect_packed's output); d_tile_info [n_tiles, 3]
+ *   int32 (left, up, scene index < n_scenes); skip_mask: bit c set = class c is left out (DOTA-1.5 container-crane);
+ *   score_mode 1: score^2 / centerness in fp32 (task1_scores, CENTERNESS != none and not CENTERNESS_USE_IN_SCORE).
+ * Row: x_k = (rint(double(v_k) * 100) / 100 + left | up) / 1.0, score = rint(double(s) * 1e4) / 1e4, i.e.
+ * float("%.2f" % v) / float("%.4f" % s) shifted as poly2origpoly does.  Order in a bucket: tile order, then the
+ * tile's row order (a stable compaction; no atomic decides a position).
+ *   d_bucket_counts [n_scenes * n_classes] int32: the bucket's TRUE row count (always written)
+ *   d_dets [n_buckets, m_cap, 9] f64, d_src [n_buckets, m_cap] int32 (tile * k_cap + row): rows at positions < m_cap.
+ * m_cap = 0 computes the counts only (d_dets / d_src may be NULL): the caller sizes m_cap from them.  n_classes <= 64.
+ * d_ws: dafne_scene_merge_workspace_bytes(n_tiles, n_classes) bytes.
+ */
+size_t dafne_scene_merge_workspace_bytes(int n_tiles, int n_classes);
+int dafne_scene_merge_rows_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap, const int32_t* d_tile_info,
+                               int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap, double* d_dets,
+                               int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

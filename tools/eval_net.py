@@ -68,6 +68,14 @@ def parse_args(argv=None):
                          "$DAFNE_DATA_DIR set -- the registered dataset of that name (dota_1_5_val_1024, hrsc_test, ucas_aod_test, ...)")
     ap.add_argument("--dataset-root", default="", help="the dataset's root directory (MetadataCatalog's root_dir in the reference)")
     ap.add_argument("--eval-dir", default="", help="output folder of --dataset-name (default OUTPUT_DIR/inference/<dataset name>)")
+    ap.add_argument("--scene-dir", default="",
+                    help="whole DOTA scenes (any size): split at rate 1 on the device (split_dota.py's grid), tile inference and "
+                         "the tile merge in one detect_scenes call; writes Task1_merged/Task1_<class>.txt and imageset.txt")
+    ap.add_argument("--task1-merged-dir", default="", help="with --scene-dir: output directory (default OUTPUT_DIR/scenes)")
+    ap.add_argument("--zip", action="store_true", help="with --scene-dir: also write task1_merged.zip (dota_evaluation.create_zip)")
+    ap.add_argument("--patch-size", type=int, default=1024, help="with --scene-dir: tile size of the split")
+    ap.add_argument("--overlap", type=int, default=200, help="with --scene-dir: tile overlap of the split")
+    ap.add_argument("--scene-batch", type=int, default=8, help="with --scene-dir: tiles per detector call")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides")
     return ap.parse_args(argv)
 
@@ -98,6 +106,76 @@ def write_synthetic_tiles(root, n, h, w, seed):
         img = (img * 220 + torch.rand(3, h, w, generator=g) * 12).clamp_(0, 255).to(torch.uint8)
         Image.fromarray(np.ascontiguousarray(img.permute(1, 2, 0).numpy())).save(
             os.path.join(root, "P%04d__1__0___%d.png" % (i // 4, 824 * (i % 4))), compress_level=3)
+
+
+def scene_args_error(args):
+    """The message --scene-dir refuses a combination with, or None."""
+    if not args.scene_dir:
+        return None
+    if args.num_gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--scene-dir runs on one GPU: sharding scenes over several GPUs is not supported"
+    if args.tta or args.tta_shard_views:
+        return "--scene-dir does not support --tta: scene-level test-time augmentation is not supported"
+    return None
+
+
+def write_zip(output_dir, merged_dir):
+    """dota_evaluation.create_zip: task1_merged.zip with the Task1_*.txt files of merged_dir at the archive's root."""
+    import glob
+    import zipfile
+    with zipfile.ZipFile(os.path.join(output_dir, "task1_merged.zip"), mode="w", compression=zipfile.ZIP_DEFLATED) as z:
+        for fname in glob.glob(merged_dir + "/Task1_*.txt"):
+            z.write(fname, arcname=os.path.basename(fname))
+
+
+def run_scenes(args):
+    """--scene-dir: every image file of the directory is one scene (decoded on host workers with read_image, BGR HWC), all of
+    them go through ONE detect_scenes call; Task1_merged/ as mergebypoly writes it for the same scenes split into tiles."""
+    from concurrent.futures import ThreadPoolExecutor
+    import dafne_amd.modeling  # noqa: F401
+    from dafne_amd.checkpoint import load_weights
+    from dafne_amd.config import load_cfg
+    from dafne_amd.data import list_image_records
+    from dafne_amd.data.loader import read_image
+    from dafne_amd.evaluation import dota_evaluation as de
+    from dafne_amd.registry import build_model
+    from dafne_amd.scene import write_task1_merged
+    from dafne_amd.utils.host import usable_cpus
+
+    cfg = load_cfg(args.config_file, args.opts)
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_net.py needs an MI355X: the HIP path has no CPU fallback")
+    dev = torch.device("cuda", 0)
+    model = build_model(cfg)
+    if args.weights or cfg.MODEL.WEIGHTS:
+        missing, unexpected = load_weights(model, args.weights or cfg.MODEL.WEIGHTS)
+        print("loaded weights: %d missing, %d unexpected keys" % (len(missing), len(unexpected)))
+    else:
+        import bench
+        model.load_state_dict(bench.seeded_state_dict(model, args.seed))
+    model.to(dev)
+    model.invalidate()
+    records = list_image_records(args.scene_dir)
+    if not records:
+        raise SystemExit("--scene-dir %s holds no image files" % args.scene_dir)
+    workers = max(1, min(args.decode_workers, usable_cpus() - 2, len(records)))
+    with ThreadPoolExecutor(workers) as pool:
+        imgs = list(pool.map(lambda r: read_image(r["file_name"], cfg.INPUT.FORMAT), records))
+    scenes = [torch.from_numpy(a).to(dev) for a in imgs]
+    res = model.detect_scenes(scenes, patch_size=args.patch_size, overlap=args.overlap, batch=args.scene_batch)
+    names = [r["image_id"] for r in records]
+    classnames = (list(de.CLASSNAMES_DOTA_1_0) + ["container-crane"])[:cfg.MODEL.DAFNE.NUM_CLASSES]
+    out = args.task1_merged_dir or os.path.join(cfg.OUTPUT_DIR, "scenes")
+    merged = os.path.join(out, "Task1_merged")
+    write_task1_merged(res, names, classnames, merged)
+    with open(os.path.join(out, "imageset.txt"), "w") as f:
+        f.write("\n".join(names))
+    if args.zip:
+        write_zip(out, merged)
+    for n, r, s in zip(names, res, scenes):
+        print("scene %s (%dx%d, %d tiles): %d detections" % (n, s.shape[0], s.shape[1], len(r["origins"]), len(r["scores"])))
+    print("Task1_merged written to %s" % merged)
+    return res
 
 
 def run(args, rank=0, world=1, local_rank=0):
@@ -297,6 +375,11 @@ def _distributed_main(args):
 
 def main(argv=None):
     args = parse_args(argv)
+    err = scene_args_error(args)
+    if err:
+        raise SystemExit("eval_net.py: " + err)
+    if args.scene_dir:
+        return run_scenes(args)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:            # under torch.distributed.run
         return _distributed_main(args)
     if args.num_gpus > 1:                                      # plain_train_net.py:660-671: launch one process per GPU
