@@ -22,6 +22,7 @@
 // fp32 arithmetic is written in the reference's operation order and this file is
 // compiled with -ffp-contract=off.
 #include "common.h"
+#include <string.h>
 
 namespace {
 
@@ -673,6 +674,156 @@ int dafne_gather_detections_hip(const float* d_corners, const float* d_scores, c
                        d_ctr, d_classes, d_locs, d_levels, d_hbox, reinterpret_cast<const long long*>(d_keep),
                        d_num_keep, d_sizes, do_postprocess, m_cap, k_cap, d_out, d_out_counts);
     return dafne::check_launch("gather");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- TTA merge candidates
+// The merge input of OneStageRCNNWithTTA (dafne/modeling/tta.py:237-262, _invert_and_concat_fast here) for many images at
+// once: every view's packed rows (detect_packed(do_postprocess=False), [k_cap, DET_ROW] + a device count) go back through
+// the inverse of the view's transforms -- un-flip (w - x), then (x * r1) * r2 with the float32 ratios, the float32
+// operations in that order -- and land in its image's Candidates rows, views in slot order, each view's rows in their own
+// order.  A view's offset is the sum of the (capped) counts of the image's earlier slots: no atomic decides a position.
+// d_overflow[image] = 1 when a view of the image reports more rows than k_cap (rows_to_instances raises there).
+namespace {
+
+__global__ void __launch_bounds__(256) tta_candidates_kernel(
+    const dafne_tta_view* __restrict__ views, const int* __restrict__ tile_beg, int k_cap, int m_cap,
+    float* __restrict__ corners, float* __restrict__ scores, float* __restrict__ ctr, int* __restrict__ classes,
+    float* __restrict__ locs, int* __restrict__ levels, float* __restrict__ hbox, int* __restrict__ counts,
+    int* __restrict__ overflow) {
+    const int img = blockIdx.x, j = blockIdx.y;
+    const int beg = tile_beg[img], nv = tile_beg[img + 1] - beg;
+    __shared__ int s_off;
+    if (j == 0 && threadIdx.x == 0) {           // the image's totals: capped row count + overflow flag
+        int tot = 0, ovf = 0;
+        for (int k = 0; k < nv; k++) {
+            const int c = *views[beg + k].d_count;
+            ovf |= (c > k_cap || c < 0);
+            tot += c < 0 ? 0 : (c > k_cap ? k_cap : c);
+        }
+        counts[img] = tot;
+        overflow[img] = ovf;
+    }
+    if (j >= nv) return;
+    const dafne_tta_view& d = views[beg + j];
+    if (threadIdx.x == 0) {
+        int off = 0;
+        for (int k = 0; k < j; k++) {
+            const int c = *views[beg + k].d_count;
+            off += c < 0 ? 0 : (c > k_cap ? k_cap : c);
+        }
+        s_off = off;
+    }
+    __syncthreads();
+    int n = *d.d_count;
+    n = n < 0 ? 0 : (n > k_cap ? k_cap : n);
+    const size_t base = (size_t)img * m_cap + s_off;
+    const float fw = d.width, fh = d.height;
+    const float rx1 = d.rx1, ry1 = d.ry1, rx2 = d.rx2, ry2 = d.ry2;
+    for (int r = threadIdx.x; r < n; r += blockDim.x) {
+        const float* src = d.d_rows + (size_t)r * DAFNE_DET_ROW;
+        const size_t o = base + r;
+        float lo_x = 0.f, hi_x = 0.f, lo_y = 0.f, hi_y = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            float x = src[2 * k], y = src[2 * k + 1];
+            if (d.flip_x) x = fw - x;
+            if (d.flip_y) y = fh - y;
+            x = x * rx1;
+            x = x * rx2;
+            y = y * ry1;
+            y = y * ry2;
+            corners[o * 8 + 2 * k] = x;
+            corners[o * 8 + 2 * k + 1] = y;
+            lo_x = k ? fminf(lo_x, x) : x;
+            hi_x = k ? fmaxf(hi_x, x) : x;
+            lo_y = k ? fminf(lo_y, y) : y;
+            hi_y = k ? fmaxf(hi_y, y) : y;
+        }
+        scores[o] = src[8];
+        ctr[o] = src[9];
+        classes[o] = (int)src[10];
+        levels[o] = (int)src[11];
+        locs[o * 2] = src[16];
+        locs[o * 2 + 1] = src[17];
+        hbox[o * 4] = lo_x;
+        hbox[o * 4 + 1] = lo_y;
+        hbox[o * 4 + 2] = hi_x;
+        hbox[o * 4 + 3] = hi_y;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dafne_tta_candidates_workspace_bytes(int n_views, int n_images) {
+    if (n_views < 1 || n_images < 1) return 0;
+    return dafne::align_up(sizeof(dafne_tta_view) * (size_t)n_views, 256) + dafne::align_up(sizeof(int) * ((size_t)n_images + 1), 256);
+}
+
+int dafne_tta_candidates_hip(const dafne_tta_view* views, int n_views, int n_images, int k_cap, int m_cap, float* d_corners,
+                             float* d_scores, float* d_ctr, int32_t* d_classes, float* d_locs, int32_t* d_levels,
+                             float* d_hbox, int32_t* d_counts, int32_t* d_overflow, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!views || n_views < 1 || n_images < 1 || k_cap < 1 || m_cap < 1 || !d_corners || !d_scores || !d_ctr || !d_classes ||
+        !d_locs || !d_levels || !d_hbox || !d_counts || !d_overflow || !d_ws)
+        return dafne::fail(DAFNE_E_INVALID, "tta_candidates: bad args (n_views %d, n_images %d, k_cap %d, m_cap %d)", n_views,
+                           n_images, k_cap, m_cap);
+    if (m_cap > 65536) return dafne::fail(DAFNE_E_UNSUPPORTED, "tta_candidates: m_cap %d above the NMS limit 65536", m_cap);
+    const size_t need = dafne_tta_candidates_workspace_bytes(n_views, n_images);
+    if (ws_bytes < need) return dafne::fail(DAFNE_E_WORKSPACE, "tta_candidates: workspace %zu < %zu", ws_bytes, need);
+    // views grouped by image, in slot order (counting sort by image, then insertion by slot inside an image)
+    int* beg = new int[n_images + 1]();
+    for (int v = 0; v < n_views; v++) {
+        const dafne_tta_view& t = views[v];
+        if (!t.d_rows || !t.d_count || t.tile < 0 || t.tile >= n_images || t.slot < 0 || (t.flip_x != 0 && t.flip_x != 1) ||
+            (t.flip_y != 0 && t.flip_y != 1)) {
+            delete[] beg;
+            return dafne::fail(DAFNE_E_INVALID, "tta_candidates: view %d: image %d slot %d flips %d/%d", v, t.tile, t.slot,
+                               t.flip_x, t.flip_y);
+        }
+        beg[t.tile + 1]++;
+    }
+    int nv_max = 0;
+    for (int i = 0; i < n_images; i++) {
+        nv_max = beg[i + 1] > nv_max ? beg[i + 1] : nv_max;
+        beg[i + 1] += beg[i];
+    }
+    if ((long long)nv_max * k_cap > m_cap) {
+        delete[] beg;
+        return dafne::fail(DAFNE_E_INVALID, "tta_candidates: %d views x k_cap %d exceed m_cap %d", nv_max, k_cap, m_cap);
+    }
+    const size_t vbytes = dafne::align_up(sizeof(dafne_tta_view) * (size_t)n_views, 256);
+    uint8_t* blob = new uint8_t[need]();
+    dafne_tta_view* td = reinterpret_cast<dafne_tta_view*>(blob);
+    int* fill = new int[n_images]();
+    int rc = DAFNE_OK;
+    for (int v = 0; v < n_views && rc == DAFNE_OK; v++) {
+        const dafne_tta_view& t = views[v];
+        int p = beg[t.tile] + fill[t.tile]++;
+        while (p > beg[t.tile] && td[p - 1].slot >= t.slot) {
+            if (td[p - 1].slot == t.slot) rc = dafne::fail(DAFNE_E_INVALID, "tta_candidates: image %d has slot %d twice", t.tile, t.slot);
+            td[p] = td[p - 1];
+            p--;
+        }
+        td[p] = t;
+    }
+    delete[] fill;
+    if (rc == DAFNE_OK) memcpy(blob + vbytes, beg, sizeof(int) * ((size_t)n_images + 1));
+    delete[] beg;
+    if (rc != DAFNE_OK) {
+        delete[] blob;
+        return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t ce = hipMemcpyAsync(d_ws, blob, need, hipMemcpyHostToDevice, st);
+    delete[] blob;
+    if (ce != hipSuccess) return dafne::fail(DAFNE_E_HIP, "tta_candidates: hipMemcpyAsync: %s", hipGetErrorString(ce));
+    hipLaunchKernelGGL(tta_candidates_kernel, dim3(n_images, nv_max > 0 ? nv_max : 1), dim3(256), 0, st, (const dafne_tta_view*)d_ws,
+                       (const int*)((uint8_t*)d_ws + vbytes), k_cap, m_cap, d_corners, d_scores, d_ctr, d_classes, d_locs,
+                       d_levels, d_hbox, d_counts, d_overflow);
+    return dafne::check_launch("tta_candidates");
 }
 
 }  // extern "C"

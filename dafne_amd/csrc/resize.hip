@@ -240,3 +240,232 @@ int dafne_scene_tiles_u8_hip(const dafne_scene_tile* tiles, int n_tiles, int pat
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------- scene TTA views
+// DotaDatasetMapperTTA's views (dafne/modeling/tta.py:71-99: per TEST.AUG size, plain / hflip / vflip) cut straight out of
+// the scenes: view v is the Pillow-exact bilinear resize of a zero-padded window of its source, then the flips, i.e. bit for
+// bit resize_u8(gather_tiles(...)[v] as CHW, out_h, out_w, hflip, vflip) (taps_for and clip8 above, the same integer sums).
+// The coefficients are computed once per launch and axis (views_taps_kernel, taps_for's fp64 operations) into the
+// workspace.  views_kernel: a workgroup owns kViewBX resampled columns x `by` resampled rows of one view; it runs the
+// horizontal pass into LDS for the source rows those rows' vertical taps touch, and then the vertical pass from LDS, so the
+// uint8 intermediate never leaves the chip.  The host picks `by` so that the LDS rows fit kViewLdsBudget.
+namespace {
+
+constexpr int kViewBX = 64;                 // resampled columns per workgroup
+constexpr int kViewLdsBudget = 48 * 1024;   // LDS per workgroup: three workgroups per CU (160 KiB)
+constexpr int kViewMaxAxes = 8;             // distinct window widths (and heights) per launch
+constexpr int kTapStride = 2 + kMaxTaps;    // per output index: xmin, n, k[kMaxTaps]
+
+struct ViewDev {
+    dafne_view_src s;
+    int tx, ty;                             // coefficient table of the x / y axis
+};
+
+struct AxisDev {
+    int in_size, out_size;
+    size_t off;                             // int offset of the table in the coefficient area
+};
+
+__global__ void __launch_bounds__(256) views_taps_kernel(const AxisDev* __restrict__ axes, int n_axes,
+                                                         int* __restrict__ coef) {
+    const int a = blockIdx.y;
+    if (a >= n_axes) return;
+    const AxisDev ax = axes[a];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ax.out_size) return;
+    Taps t;
+    taps_for(i, ax.in_size, ax.out_size, t);
+    int* c = coef + ax.off + (size_t)i * kTapStride;
+    c[0] = t.xmin;
+    c[1] = t.n;
+    for (int x = 0; x < t.n; x++) c[2 + x] = t.k[x];
+}
+
+// window pixel (r, x), channel ch of the view's source; 0 outside the source (the split's zero padding)
+__device__ __forceinline__ int window_px(const dafne_view_src& s, int r, int x, int ch) {
+    const long long sy = (long long)s.up + r, sx = (long long)s.left + x;
+    if (sy >= s.h || sx >= s.w) return 0;
+    return s.layout_hwc ? s.d_src[((size_t)sy * s.w + sx) * 3 + ch] : s.d_src[((size_t)ch * s.h + sy) * s.w + sx];
+}
+
+__global__ void __launch_bounds__(256) views_kernel(const ViewDev* __restrict__ views, int n_views, const AxisDev* __restrict__ axes,
+                                                    const int* __restrict__ coef, int out_h, int out_w, int by, int rows_cap,
+                                                    uint8_t* __restrict__ out) {
+    extern __shared__ uint8_t tmp[];         // [3][rows_cap][kViewBX]
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * kViewBX, y0 = blockIdx.y * by;
+    const int nx = min(kViewBX, out_w - x0), ny = min(by, out_h - y0);
+    for (int v = blockIdx.z; v < n_views; v += gridDim.z) {
+        const ViewDev vd = views[v];
+        const dafne_view_src& s = vd.s;
+        const int* cx = coef + axes[vd.tx].off;
+        const int* cy = coef + axes[vd.ty].off;
+        // source rows of the block's vertical taps: xmin is non-decreasing in the output index, and so is xmin + n
+        const int ylo = cy[(size_t)y0 * kTapStride];
+        const int* clast = cy + (size_t)(y0 + ny - 1) * kTapStride;
+        const int nrows = min(clast[0] + clast[1] - ylo, rows_cap);
+        // horizontal pass: rows [ylo, ylo + nrows) x the block's columns -> LDS
+        for (int e = tid; e < nrows * kViewBX; e += blockDim.x) {
+            const int r = e / kViewBX, c = e - r * kViewBX;
+            if (c >= nx) continue;
+            const int* t = cx + (size_t)(x0 + c) * kTapStride;
+            const int xmin = t[0], n = t[1];
+            int a0 = 1 << (kPrec - 1), a1 = a0, a2 = a0;
+            for (int x = 0; x < n; x++) {
+                const int k = t[2 + x];
+                a0 += window_px(s, ylo + r, xmin + x, 0) * k;
+                a1 += window_px(s, ylo + r, xmin + x, 1) * k;
+                a2 += window_px(s, ylo + r, xmin + x, 2) * k;
+            }
+            tmp[(0 * rows_cap + r) * kViewBX + c] = clip8(a0);
+            tmp[(1 * rows_cap + r) * kViewBX + c] = clip8(a1);
+            tmp[(2 * rows_cap + r) * kViewBX + c] = clip8(a2);
+        }
+        __syncthreads();
+        // vertical pass + flips folded into the store index
+        for (int e = tid; e < ny * kViewBX; e += blockDim.x) {
+            const int yl = e / kViewBX, c = e - yl * kViewBX;
+            if (c >= nx) continue;
+            const int yy = y0 + yl, xx = x0 + c;
+            const int* t = cy + (size_t)yy * kTapStride;
+            const int r0 = t[0] - ylo, n = t[1];
+            int a0 = 1 << (kPrec - 1), a1 = a0, a2 = a0;
+            for (int y = 0; y < n; y++) {
+                const int k = t[2 + y];
+                const int r = r0 + y < rows_cap ? r0 + y : rows_cap - 1;     // (never clamps: rows_cap bounds the span)
+                a0 += (int)tmp[(0 * rows_cap + r) * kViewBX + c] * k;
+                a1 += (int)tmp[(1 * rows_cap + r) * kViewBX + c] * k;
+                a2 += (int)tmp[(2 * rows_cap + r) * kViewBX + c] * k;
+            }
+            const int oy = s.vflip ? out_h - 1 - yy : yy, ox = s.hflip ? out_w - 1 - xx : xx;
+            const size_t plane = (size_t)out_h * out_w;
+            uint8_t* o = out + (size_t)v * 3 * plane + (size_t)oy * out_w + ox;
+            o[0] = clip8(a0);
+            o[plane] = clip8(a1);
+            o[2 * plane] = clip8(a2);
+        }
+        __syncthreads();
+    }
+}
+
+// the distinct window widths / heights of a launch -> axis tables; false when there are more than kViewMaxAxes of either
+bool view_axes(const dafne_view_src* views, int n_views, int out_h, int out_w, AxisDev* axes, int* n_axes, int* tx, int* ty) {
+    int na = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        const int first = na;
+        for (int v = 0; v < n_views; v++) {
+            const int in = pass ? views[v].win_h : views[v].win_w;
+            int a = first;
+            while (a < na && axes[a].in_size != in) a++;
+            if (a == na) {
+                if (na - first >= kViewMaxAxes) return false;
+                axes[na].in_size = in;
+                axes[na].out_size = pass ? out_h : out_w;
+                na++;
+            }
+            (pass ? ty : tx)[v] = a;
+        }
+    }
+    size_t off = 0;
+    for (int a = 0; a < na; a++) {
+        axes[a].off = off;
+        off += (size_t)axes[a].out_size * kTapStride;
+    }
+    *n_axes = na;
+    return true;
+}
+
+// rows of the LDS intermediate a workgroup of `by` resampled rows needs, for the largest vertical scale of the launch:
+// the span ylo .. xmin + n of rows y0 .. y0 + by - 1 is at most (by - 1) * scale + 2 * support + 1 (taps_for's rounding)
+int view_rows_cap(double scale, int by, int in_max) {
+    const double support = scale < 1.0 ? 1.0 : scale;
+    int r = (int)((by - 1) * scale + 2.0 * support + 1.0) + 2;
+    return r < in_max ? r : in_max;
+}
+
+size_t views_header_bytes(int n_views) {
+    return dafne::align_up(sizeof(ViewDev) * (size_t)n_views, 256) + dafne::align_up(sizeof(AxisDev) * 2 * kViewMaxAxes, 256);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dafne_scene_views_workspace_bytes(const dafne_view_src* views, int n_views, int out_h, int out_w) {
+    if (!views || n_views < 1 || out_h < 1 || out_w < 1) return 0;
+    AxisDev axes[2 * kViewMaxAxes];
+    int na = 0;
+    int* tx = new int[n_views];
+    int* ty = new int[n_views];
+    const bool ok = view_axes(views, n_views, out_h, out_w, axes, &na, tx, ty);
+    delete[] tx;
+    delete[] ty;
+    if (!ok) return 0;
+    size_t coef = 0;
+    for (int a = 0; a < na; a++) coef += (size_t)axes[a].out_size * kTapStride;
+    return views_header_bytes(n_views) + dafne::align_up(coef * sizeof(int), 256);
+}
+
+int dafne_scene_views_u8_hip(const dafne_view_src* views, int n_views, int out_h, int out_w, uint8_t* d_out, void* d_ws,
+                             size_t ws_bytes, void* stream) {
+    if (!views || !d_out || !d_ws || n_views < 1 || out_h < 1 || out_w < 1)
+        return dafne::fail(DAFNE_E_INVALID, "scene_views: bad args (n_views %d, out %dx%d)", n_views, out_h, out_w);
+    double sy_max = 0.0;
+    int in_h_max = 1;
+    for (int v = 0; v < n_views; v++) {
+        const dafne_view_src& s = views[v];
+        if (!s.d_src || s.h < 1 || s.w < 1 || (s.layout_hwc != 0 && s.layout_hwc != 1) || s.left < 0 || s.up < 0 ||
+            s.win_h < 1 || s.win_w < 1 || (s.hflip != 0 && s.hflip != 1) || (s.vflip != 0 && s.vflip != 1))
+            return dafne::fail(DAFNE_E_INVALID, "scene_views: view %d: source %dx%d layout %d window (%d, %d) %dx%d flips %d/%d", v,
+                               s.h, s.w, s.layout_hwc, s.left, s.up, s.win_h, s.win_w, s.hflip, s.vflip);
+        // the limit of dafne_resize_bilinear_u8_hip: tap count of the widest filter, 2 * ceil(support) + 1
+        const double sx = (double)s.win_w / out_w, sy = (double)s.win_h / out_h;
+        if ((sx > 1 ? sx : 1) * 2 + 2 > kMaxTaps || (sy > 1 ? sy : 1) * 2 + 2 > kMaxTaps)
+            return dafne::fail(DAFNE_E_UNSUPPORTED, "scene_views: view %d: downscale factor above %d", v, kMaxTaps / 2 - 1);
+        if (sy > sy_max) sy_max = sy;
+        if (s.win_h > in_h_max) in_h_max = s.win_h;
+    }
+    const size_t need = dafne_scene_views_workspace_bytes(views, n_views, out_h, out_w);
+    if (need == 0) return dafne::fail(DAFNE_E_UNSUPPORTED, "scene_views: more than %d window widths or heights in one launch", kViewMaxAxes);
+    if (ws_bytes < need) return dafne::fail(DAFNE_E_WORKSPACE, "scene_views: workspace %zu < %zu", ws_bytes, need);
+    // header: views + axis tables, one copy
+    const size_t hdr = views_header_bytes(n_views);
+    const size_t vbytes = dafne::align_up(sizeof(ViewDev) * (size_t)n_views, 256);
+    uint8_t* blob = new uint8_t[hdr]();
+    ViewDev* vd = reinterpret_cast<ViewDev*>(blob);
+    AxisDev* axes = reinterpret_cast<AxisDev*>(blob + vbytes);
+    int na = 0;
+    int* tx = new int[n_views];
+    int* ty = new int[n_views];
+    view_axes(views, n_views, out_h, out_w, axes, &na, tx, ty);
+    for (int v = 0; v < n_views; v++) {
+        vd[v].s = views[v];
+        vd[v].tx = tx[v];
+        vd[v].ty = ty[v];
+    }
+    delete[] tx;
+    delete[] ty;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t ce = hipMemcpyAsync(d_ws, blob, hdr, hipMemcpyHostToDevice, st);
+    delete[] blob;
+    if (ce != hipSuccess) return dafne::fail(DAFNE_E_HIP, "scene_views: hipMemcpyAsync: %s", hipGetErrorString(ce));
+    const ViewDev* d_views = (const ViewDev*)d_ws;
+    const AxisDev* d_axes = (const AxisDev*)((uint8_t*)d_ws + vbytes);
+    int* d_coef = (int*)((uint8_t*)d_ws + hdr);
+    const int omax = out_h > out_w ? out_h : out_w;
+    hipLaunchKernelGGL(views_taps_kernel, dim3((omax + 255) / 256, na), dim3(256), 0, st, d_axes, na, d_coef);
+    int rc = dafne::check_launch("scene_views_taps");
+    if (rc) return rc;
+    // rows per workgroup: the most that keep the LDS intermediate within the budget
+    int by = 32, rows_cap = view_rows_cap(sy_max, by, in_h_max);
+    while (by > 1 && 3 * kViewBX * rows_cap > kViewLdsBudget) {
+        by /= 2;
+        rows_cap = view_rows_cap(sy_max, by, in_h_max);
+    }
+    const unsigned gz = (unsigned)(n_views < 65535 ? n_views : 65535);
+    hipLaunchKernelGGL(views_kernel, dim3((out_w + kViewBX - 1) / kViewBX, (out_h + by - 1) / by, gz), dim3(256),
+                       (size_t)3 * kViewBX * rows_cap, st, d_views, n_views, d_axes, d_coef, out_h, out_w, by, rows_cap, d_out);
+    return dafne::check_launch("scene_views");
+}
+
+}  // extern "C"

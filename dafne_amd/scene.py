@@ -16,7 +16,20 @@ strict hull test).  write_task1_merged then writes what mergebypoly writes, byte
   merge_tile_rows(...)                          tile rows -> per-(scene, class) f64 merge rows + back-index
   merge_scenes(...)                             the above + NMS + the kept rows per scene
   detect_scenes(model, scenes, ...)             OneStageDetector.detect_scenes
+  scene_views(srcs, out_h, out_w)               TTA views cut from scenes / tiles: [V, 3, out_h, out_w] uint8, one launch
+  tta_view_table(mapper, h, w, orig_hw)         per view: its resize target, flips and inverse transform (host)
+  tta_candidates(views, n_images, k_cap)        per-view packed rows -> the TTA merge's Candidates (device, one launch)
+  tta_tile_rows(tta, scenes, ...)               every tile's merged TTA rows
+  detect_scenes_tta(tta, scenes, ...)           OneStageRCNNWithTTA.detect_scenes
   write_task1_merged(results, names, classes, dst)
+
+Scene-level TTA runs the per-image TTA of every tile (modeling/tta.py: DotaDatasetMapperTTA's views, detect_packed without
+post-process, the inverse transforms, one rotated NMS + cap per tile) with views of many tiles batched: per TTA size one
+dafne_scene_views_u8_hip launch cuts and resamples the plain / hflip / vflip views of all tiles of a batch straight from
+the scenes (no tile files, no per-view resize calls), detect_packed runs them in calls that keep the per-image path's view
+chunks (a few tiles per call), and dafne_tta_candidates_hip maps
+every view's rows back into its tile's merge candidates on the device, where pp.select / pp.gather finish the merge.
+The tiles' merged rows then go through merge_scenes like detect_scenes' tile rows.
 """
 import os
 
@@ -28,6 +41,9 @@ from . import _lib
 NMS_THRESH = 0.1          # ResultMerge_multi_process.py:22
 # NMS workspace per launch: the buckets of a call are cut into launches of at most this many bytes
 _NMS_WS_LIMIT = 1 << 31
+# scene TTA: views per detector call, whole tiles' share of a view chunk (R101, 27 views, batch 8 on one MI355X: 6 / 9 / 24
+# views per call ran at 1.14 / 0.98 / 0.72x the per-tile route; scripts/scene_bench.py --tta --views-per-call)
+_TTA_VIEWS_PER_CALL = 6
 
 
 def split_origins(h, w, patch_size=1024, overlap=200, rate=1):
@@ -118,10 +134,11 @@ def skip_mask(cfg):
     return (1 << 15) if bool(cfg.DATASETS.DOTA_REMOVE_CONTAINER_CRANE) else 0
 
 
-def merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, m_cap=None):
+def merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, m_cap=None, overflow=None):
     """rows [T,k_cap,18] f32 + counts [T] (device) + tile_info [T,3] int32 (left, up, scene) -> (dets [B,m_cap,9] f64,
     bucket counts [B] int32, src [B,m_cap] int32, m_cap) with B = n_scenes * n_classes.  m_cap None: sized from the bucket
-    counts (a host read of B integers)."""
+    counts (a host read of B integers).  overflow: optional device int tensor, read in that same host read; nonzero
+    raises (rows the caller truncated)."""
     L = _lib.load()
     dev = rows.device
     T, k_cap = int(rows.shape[0]), int(rows.shape[1])
@@ -145,7 +162,13 @@ def merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_
                        "dafne_scene_merge_rows_hip")
         if m_cap is None:
             call(0, None, None)
-            m_cap = max(int(bcount.max().item()), 1)
+            if overflow is None:
+                m_cap = max(int(bcount.max().item()), 1)
+            else:
+                mx, ovf = torch.stack([bcount.max(), overflow.to(torch.int32).max()]).cpu().tolist()
+                if ovf:
+                    raise _lib.DafneHipError("tile detections exceed the packed row capacity (%d): rows would be dropped" % k_cap)
+                m_cap = max(int(mx), 1)
         dets = torch.empty((nb, m_cap, 9), dtype=torch.float64, device=dev)
         src = torch.empty((nb, m_cap), dtype=torch.int32, device=dev)
         call(m_cap, dets, src)
@@ -175,11 +198,13 @@ def nms_buckets(dets, bcount, m_cap, thresh=NMS_THRESH):
     return keep, nk
 
 
-def merge_scenes(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0):
+def merge_scenes(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, overflow=None):
     """Tile rows -> per scene {"corners" [K,8] f64, "scores" [K] f64, "labels" [K] int64, "tile" [K], "row" [K]}: class by
-    class, each class in the NMS keep order (descending score) -- what mergebypoly writes for that scene."""
+    class, each class in the NMS keep order (descending score) -- what mergebypoly writes for that scene.  overflow: see
+    merge_tile_rows."""
     k_cap = int(rows.shape[1])
-    dets, bcount, src, m_cap = merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip, score_mode)
+    dets, bcount, src, m_cap = merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip, score_mode,
+                                               overflow=overflow)
     keep, nk = nms_buckets(dets, bcount, m_cap)
     dev = dets.device
     nb = dets.shape[0]
@@ -237,6 +262,265 @@ def detect_scenes(model, scenes, patch_size=1024, overlap=200, batch=8, layout_h
         rows = torch.cat([r for r, _ in parts])
         counts = torch.cat([c for _, c in parts])
         res = merge_scenes(rows, counts, info, len(scenes), int(cfg.MODEL.DAFNE.NUM_CLASSES), skip_mask(cfg), task1_score_mode(cfg))
+    for r, org in zip(res, origins):
+        r["origins"] = org
+    return res
+
+
+def scene_views(srcs, out_h, out_w):
+    """srcs: per view (img, layout_hwc, left, up, win_h, win_w, hflip, vflip), img a device uint8 BGR image ([H,W,3] with
+    layout_hwc, else [3,H,W]) -> [V, 3, out_h, out_w] uint8: view v is resize_u8 of the zero-padded win_h x win_w window at
+    (left, up), flipped -- bit for bit -- in one launch."""
+    L = _lib.load()
+    n = len(srcs)
+    if n == 0:
+        raise ValueError("scene_views: no views")
+    arr = (_lib.ViewSrc * n)()
+    keep = []
+    for k, (img, hwc, left, up, wh, ww, hf, vf) in enumerate(srcs):
+        if not img.is_cuda:
+            raise _lib.DafneHipError("scene_views: the MI355X engine has no CPU path (got a CPU image)")
+        h, w, hwc = scene_layout(img, hwc)
+        img = img.contiguous()
+        keep.append(img)
+        a = arr[k]
+        a.d_src, a.h, a.w, a.layout_hwc, a.left, a.up = img.data_ptr(), h, w, int(hwc), int(left), int(up)
+        a.win_h, a.win_w, a.hflip, a.vflip = int(wh), int(ww), int(bool(hf)), int(bool(vf))
+    dev = keep[0].device
+    with torch.cuda.device(dev):
+        out = torch.empty((n, 3, int(out_h), int(out_w)), dtype=torch.uint8, device=dev)
+        nbytes = L.dafne_scene_views_workspace_bytes(arr, n, int(out_h), int(out_w))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.dafne_scene_views_u8_hip(arr, n, int(out_h), int(out_w), _lib.ptr(out), _lib.ptr(ws), nbytes,
+                                              _lib.current_stream()), "dafne_scene_views_u8_hip")
+    return out
+
+
+def tta_view_table(mapper, h, w, orig_hw):
+    """The views of an (h, w) loader image whose original is orig_hw, in DotaDatasetMapperTTA.view_specs' order: per view
+    (new_h, new_w, hflip, vflip, width, height, rx1, ry1, rx2, ry2) -- the pixels' resize target and flips, and the inverse
+    of the view's transform list as _invert_and_concat_fast applies it: un-flip by width / height, then (x * rx1) * rx2, the
+    ratios float32 of the python double (1 where there is no pre-resize)."""
+    from .modeling.tta import HFlipT, ResizeT, VFlipT
+    out = []
+    for nh, nw, tfl in mapper.view_specs(int(h), int(w), tuple(int(v) for v in orig_hw)):
+        ops = list(tfl.tfms)
+        hf = vf = False
+        wv = hv = 0.0
+        if ops and isinstance(ops[-1], HFlipT):
+            hf, wv = True, float(ops.pop().width)
+        elif ops and isinstance(ops[-1], VFlipT):
+            vf, hv = True, float(ops.pop().height)
+        if not ops or len(ops) > 2 or not all(isinstance(t, ResizeT) for t in ops):
+            raise NotImplementedError("scene TTA: a view transform other than [pre-resize,] resize [, one flip]")
+        inv = [t.inverse() for t in reversed(ops)]           # un-resize of the view first, then of the pre-resize
+        rx = [t.new_w * 1.0 / t.w for t in inv] + [1.0]
+        ry = [t.new_h * 1.0 / t.h for t in inv] + [1.0]
+        f32 = np.float32
+        out.append((int(nh), int(nw), hf, vf, f32(wv), f32(hv), f32(rx[0]), f32(ry[0]), f32(rx[1]), f32(ry[1])))
+    return out
+
+
+def tta_candidates(views, n_images, k_cap, m_cap=None):
+    """views: per view (rows [k_cap, 18] f32 device view, count [1] int32 device view, image, slot, table row of
+    tta_view_table) -> (postprocess.Candidates [n_images, m_cap], overflow [n_images] int32), one launch.  m_cap None:
+    k_cap x the most views of one image."""
+    from . import postprocess as pp
+    L = _lib.load()
+    n = len(views)
+    if n == 0:
+        raise ValueError("tta_candidates: no views")
+    per = {}
+    for v in views:
+        per[v[2]] = per.get(v[2], 0) + 1
+    if m_cap is None:
+        m_cap = int(k_cap) * max(per.values())
+    arr = (_lib.TtaView * n)()
+    dev = views[0][0].device
+    for k, (rows, cnt, img, slot, t) in enumerate(views):
+        if rows.dtype != torch.float32 or rows.dim() != 2 or tuple(rows.shape) != (k_cap, _lib.DET_ROW) or not rows.is_contiguous():
+            raise ValueError("tta_candidates: rows of a view must be contiguous float32 [%d, %d]" % (k_cap, _lib.DET_ROW))
+        if cnt.dtype != torch.int32:
+            raise ValueError("tta_candidates: counts must be int32")
+        a = arr[k]
+        a.d_rows, a.d_count, a.tile, a.slot = rows.data_ptr(), cnt.data_ptr(), int(img), int(slot)
+        a.flip_x, a.flip_y, a.width, a.height = int(t[2]), int(t[3]), float(t[4]), float(t[5])
+        a.rx1, a.ry1, a.rx2, a.ry2 = float(t[6]), float(t[7]), float(t[8]), float(t[9])
+    with torch.cuda.device(dev):
+        cand = pp.Candidates(int(n_images), int(m_cap), dev)
+        ovf = torch.empty(int(n_images), dtype=torch.int32, device=dev)
+        nbytes = L.dafne_tta_candidates_workspace_bytes(n, int(n_images))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.dafne_tta_candidates_hip(arr, n, int(n_images), int(k_cap), int(m_cap), _lib.ptr(cand.corners),
+                                              _lib.ptr(cand.scores), _lib.ptr(cand.ctr), _lib.ptr(cand.classes),
+                                              _lib.ptr(cand.locs), _lib.ptr(cand.levels), _lib.ptr(cand.hbox),
+                                              _lib.ptr(cand.counts), _lib.ptr(ovf), _lib.ptr(ws), nbytes, _lib.current_stream()),
+                   "dafne_tta_candidates_hip")
+    return cand, ovf
+
+
+class _CandSlice:
+    """Images [i0, i1) of a Candidates (views of its tensors) for pp.select."""
+
+    def __init__(self, cand, i0, i1):
+        self.n, self.m_cap = i1 - i0, cand.m_cap
+        for f in ("corners", "scores", "ctr", "classes", "locs", "levels", "hbox", "counts"):
+            setattr(self, f, getattr(cand, f)[i0:i1])
+
+
+def tta_select(cand, nms_thresh, post_topk):
+    """pp.select over every image of `cand`, cut into launches whose NMS workspace stays under the limit nms_buckets uses."""
+    from . import postprocess as pp
+    L = _lib.load()
+    per = max(L.dafne_poly_nms_workspace_bytes(1, cand.m_cap), 1)
+    step = max(1, min(cand.n, _NMS_WS_LIMIT // per))
+    if step >= cand.n:
+        return pp.select(cand, nms_thresh, post_topk)
+    parts = [pp.select(_CandSlice(cand, i0, min(i0 + step, cand.n)), nms_thresh, post_topk) for i0 in range(0, cand.n, step)]
+    return torch.cat([k for k, _ in parts]), torch.cat([c for _, c in parts])
+
+
+def _tta_scene_plan(tta, scenes, patch_size, overlap, layout_hwc):
+    from .data.loader import inference_resize_shape
+    m = tta.model
+    cfg = m.cfg
+    outs = m.proposal_generator.dafne_outputs
+    if not outs.nms_thresh > 0:
+        raise NotImplementedError("scene TTA with MODEL.DAFNE.NMS_TH <= 0 (the merge without NMS) is not supported")
+    if len(getattr(tta.tta_mapper, "rotation_angles", ())):
+        raise NotImplementedError("rotation TTA is not supported")
+    patch = int(patch_size)
+    origins, tiles = [], []
+    for s, img in enumerate(scenes):
+        h, w, hwc = scene_layout(img, layout_hwc)
+        org = split_origins(h, w, patch, overlap)
+        origins.append(org)
+        tiles.extend((s, left, up, h, w, hwc) for left, up in org)
+    nh, nw = inference_resize_shape(cfg, patch, patch)
+    table = tta_view_table(tta.tta_mapper, nh, nw, (patch, patch))
+    k_cap = outs.packed_k_cap()
+    if k_cap * len(table) > 65536:
+        raise NotImplementedError("scene TTA: %d views x %d rows per view exceed the rotated NMS's 65536 candidates"
+                                  % (len(table), k_cap))
+    # the per-image path's chunks (_batch_inference_packed: `batch_size` consecutive views per detector call, a chunk of
+    # several sizes zero-padded to its largest view): a view's rows depend on its chunk's padded shape, so chunk j of every
+    # tile of a batch goes through one detector call.  With 3 views per size (the released AUG) a chunk is one size.
+    bs = max(1, int(tta.batch_size))
+    chunks = [(a, min(a + bs, len(table))) for a in range(0, len(table), bs)]
+    return patch, origins, tiles, (nh, nw), table, chunks
+
+
+def tta_tile_rows(tta, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None):
+    """Every tile's merged TTA rows: (rows [T, k_cap, 18] f32, counts [T] int32, overflow [1] int32 -- all on the device --,
+    tile_info [(left, up, scene)], origins per scene).  Tile t's rows[t, :counts[t]] are OneStageRCNNWithTTA's merged
+    Instances of that tile (corners, scores, centerness, classes in keep order).  The host does not wait for the result.
+
+    Batch b + 1's views and detector calls are enqueued before batch b's merge: the merge's descriptor upload (a pageable
+    copy) returns once the caller's stream has reached it, i.e. after batch b's detections, and by then batch b + 1 keeps the
+    GPU busy.  (A stream of its own for the views measured far slower, 0.24x the per-tile route.)"""
+    from . import postprocess as pp
+    from .data.loader import _to_chw_resized
+    m = tta.model
+    dev = m.device
+    outs = m.proposal_generator.dafne_outputs
+    with torch.cuda.device(dev):
+        main = torch.cuda.current_stream()
+        scenes = [x.to(dev).contiguous() for x in scenes]
+        patch, origins, tiles, (nh, nw), table, chunks = _tta_scene_plan(tta, scenes, patch_size, overlap, layout_hwc)
+        pre = (nh, nw) != (patch, patch)
+        k_out = outs.packed_k_cap()
+
+        def enqueue(bt):
+            n = len(bt)
+            if pre:
+                # the test loader's resize of a tile file (data.loader.DAFNeTestMapper.finish); the views resample that image
+                org = [[] for _ in scenes]
+                for s, left, up, _, _, _ in bt:
+                    org[s].append((left, up))
+                hwc = gather_tiles(scenes, org, patch, layout_hwc)
+                order = sorted(range(n), key=lambda i: bt[i][0])          # gather_tiles returns the tiles scene by scene
+                srcs = [None] * n
+                for j, i in enumerate(order):
+                    srcs[i] = (_to_chw_resized(hwc[j], nh, nw), False, 0, 0, nh, nw)
+            else:
+                srcs = [(scenes[s], hwc, left, up, patch, patch) for s, left, up, _, _, hwc in bt]
+            # detector calls of at most _TTA_VIEWS_PER_CALL views (whole tiles' chunks); they rotate over the compute streams as
+            # in _views_packed: two for calls of 6 views or more, else three
+            tpc = [max(1, min(n, _TTA_VIEWS_PER_CALL // (e - a))) for a, e in chunks]
+            nstreams = 2 if max((e - a) * t for (a, e), t in zip(chunks, tpc)) >= 6 else 3
+            pending = []
+            ncall = 0
+            for j, (a, e) in enumerate(chunks):
+                shapes = [table[k][:2] for k in range(a, e)]
+                hw = [shapes[k - a] for src in srcs for k in range(a, e)]          # tile-major: tile i's views of the chunk
+                if len(set(shapes)) == 1:
+                    vh, vw = shapes[0]
+                    x = scene_views([src + (table[k][2], table[k][3]) for src in srcs for k in range(a, e)], vh, vw)
+                else:                        # one views launch per size of the chunk, zero-padded into the chunk's batch
+                    x = torch.zeros(len(hw), 3, max(h for h, _ in hw), max(w for _, w in hw), dtype=torch.uint8, device=dev)
+                    for vh, vw in sorted(set(shapes)):
+                        ks = [k for k in range(a, e) if shapes[k - a] == (vh, vw)]
+                        y = scene_views([src + (table[k][2], table[k][3]) for src in srcs for k in ks], vh, vw)
+                        q = 0
+                        for i in range(n):
+                            for k in ks:
+                                x[i * (e - a) + k - a, :, :vh, :vw] = y[q]
+                                q += 1
+                # the arguments of OneStageRCNNWithTTA._views_packed: every view's rows are the per-image path's rows
+                for t0 in range(0, n, tpc[j]):
+                    t1 = min(n, t0 + tpc[j])
+                    v0, v1 = t0 * (e - a), t1 * (e - a)
+                    rows, counts = m.detect_packed(x[v0:v1], valid_hw=hw[v0:v1], out_hw=[(patch, patch)] * (v1 - v0),
+                                                   do_postprocess=False, graphs=False, pipelined=True, splits=1,
+                                                   stream_offset=ncall % nstreams)
+                    ncall += 1
+                    pending.append((a, e, t0, t1, rows, counts))
+            done = torch.cuda.Event()
+            done.record(m.side_stream)
+            return n, pending, done
+
+        def finish(state):
+            n, pending, done = state
+            main.wait_event(done)
+            views = []
+            for a, e, t0, t1, rows, counts in pending:
+                rows.record_stream(main)
+                counts.record_stream(main)
+                q = 0
+                for i in range(t0, t1):
+                    for k in range(a, e):
+                        views.append((rows[q], counts[q:q + 1], i, k, table[k]))
+                        q += 1
+            cand, ovf = tta_candidates(views, n, int(pending[0][4].shape[1]))
+            keep, nk = tta_select(cand, outs.nms_thresh, max(outs.post_nms_topk, 0))
+            r, c = pp.gather(cand, keep, nk, sizes=None, k_cap=k_out)
+            return r, c, torch.maximum(ovf.max(), (c > k_out).to(torch.int32).max())
+
+        done_parts, prev = [], None
+        for b0 in range(0, len(tiles), max(1, int(batch))):
+            cur = enqueue(tiles[b0:b0 + batch])
+            if prev is not None:
+                done_parts.append(finish(prev))
+            prev = cur
+        done_parts.append(finish(prev))
+        rows = torch.cat([r for r, _, _ in done_parts])
+        counts = torch.cat([c for _, c, _ in done_parts])
+        overflow = torch.stack([f for _, _, f in done_parts]).max().reshape(1)
+    info = [(left, up, s) for s, left, up, _, _, _ in tiles]
+    return rows, counts, overflow, info, origins
+
+
+def detect_scenes_tta(tta, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None):
+    """OneStageRCNNWithTTA.detect_scenes: device uint8 BGR scenes -> merge_scenes' dicts per scene (plus "origins"); "tile" /
+    "row" index the tiles' merged TTA rows.  The host reads what merge_scenes reads (and the overflow flag with it)."""
+    if not scenes:
+        return []
+    m = tta.model
+    cfg = m.cfg
+    rows, counts, overflow, info, origins = tta_tile_rows(tta, scenes, patch_size, overlap, batch, layout_hwc)
+    with torch.cuda.device(m.device):
+        res = merge_scenes(rows, counts, info, len(scenes), int(cfg.MODEL.DAFNE.NUM_CLASSES), skip_mask(cfg),
+                           task1_score_mode(cfg), overflow=overflow)
     for r, org in zip(res, origins):
         r["origins"] = org
     return res

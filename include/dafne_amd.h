@@ -577,6 +577,56 @@ int dafne_scene_merge_rows_hip(const float* d_rows, const int32_t* d_counts, int
                                int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap, double* d_dets,
                                int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream);
 
+/*
+ * TTA views cut straight from the scenes (DotaDatasetMapperTTA, dafne/modeling/tta.py:71-99: per TEST.AUG size, plain /
+ * hflip / vflip).  View v = Pillow's BILINEAR resize of the win_h x win_w window of its source at (left, up) to
+ * out_h x out_w, then the flips; window pixels past the source read as 0 (the split's padding=True).  Bit for bit
+ * dafne_resize_bilinear_u8_hip of the zero-padded crop (dafne_scene_tiles_u8_hip) with the same flips, including out ==
+ * window (flips only) and upscales.  Two kinds of source: a scene with the window set to a tile, or an already resized
+ * tile with the window set to the whole image.
+ *   views: HOST array of n_views descriptors (checked on the host, copied into d_ws on `stream`); d_src uint8 BGR
+ *   [h,w,3] (layout_hwc = 1) or [3,h,w] (= 0), left, up >= 0, hflip / vflip 0 or 1.
+ *   d_out: [n_views, 3, out_h, out_w] uint8 CHW (detect_packed's batch).
+ * A downscale beyond dafne_resize_bilinear_u8_hip's tap limit, or more than 8 distinct window widths (or heights) in one
+ * call -> DAFNE_E_UNSUPPORTED.  d_ws: dafne_scene_views_workspace_bytes(views, n_views, out_h, out_w) bytes (the
+ * descriptors and the coefficient tables, computed once per call and axis); 0 = unsupported arguments.
+ */
+typedef struct dafne_view_src {
+    const uint8_t* d_src;
+    int32_t h, w, layout_hwc;
+    int32_t left, up, win_h, win_w;
+    int32_t hflip, vflip, reserved;
+} dafne_view_src;
+size_t dafne_scene_views_workspace_bytes(const dafne_view_src* views, int n_views, int out_h, int out_w);
+int dafne_scene_views_u8_hip(const dafne_view_src* views, int n_views, int out_h, int out_w, uint8_t* d_out, void* d_ws,
+                             size_t ws_bytes, void* stream);
+/*
+ * The merge input of OneStageRCNNWithTTA (dafne/modeling/tta.py:237-262) for n_images images on the device: every view's
+ * packed rows (detect_packed(do_postprocess=False): d_rows [k_cap, DAFNE_DET_ROW] f32 + *d_count, device pointers per
+ * view, so the chunks of several detector calls need no concatenation) back through the inverse of the view's transforms:
+ * x' = ((flip_x ? width - x : x) * rx1) * rx2, y' likewise with flip_y / height / ry1 / ry2, float32 in that order (rx1:
+ * view -> loader image, rx2: loader image -> original image, float32 of the double ratio; 1 where there is none).
+ * Output: the Candidates layout of dafne_decode_levels_hip, [n_images, m_cap] rows: corners (8), scores, ctr, classes,
+ * locs (2), levels copied from the row, hbox = min / max of the mapped corners; d_counts [n_images] = the image's rows.
+ * Order: per image the views in slot order (slot = position in the mapper's view order), each view's rows in their own
+ * order; a view's offset is the prefix of the earlier slots' counts (no atomic decides a position).  (image, slot) pairs
+ * must be unique; views per image x k_cap <= m_cap <= 65536 (the rotated NMS's limit).
+ * d_overflow [n_images] int32: 1 where a view's count is above k_cap (its rows are truncated: the caller must raise).
+ * views: HOST array (copied into d_ws on `stream`); d_ws: dafne_tta_candidates_workspace_bytes(n_views, n_images) bytes.
+ */
+typedef struct dafne_tta_view {
+    const float* d_rows;
+    const int32_t* d_count;
+    int32_t tile, slot;
+    int32_t flip_x, flip_y;
+    float width, height;
+    float rx1, ry1, rx2, ry2;
+} dafne_tta_view;
+size_t dafne_tta_candidates_workspace_bytes(int n_views, int n_images);
+int dafne_tta_candidates_hip(const dafne_tta_view* views, int n_views, int n_images, int k_cap, int m_cap, float* d_corners,
+                             float* d_scores, float* d_ctr, int32_t* d_classes, float* d_locs, int32_t* d_levels,
+                             float* d_hbox, int32_t* d_counts, int32_t* d_overflow, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

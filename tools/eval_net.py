@@ -76,6 +76,9 @@ def parse_args(argv=None):
     ap.add_argument("--patch-size", type=int, default=1024, help="with --scene-dir: tile size of the split")
     ap.add_argument("--overlap", type=int, default=200, help="with --scene-dir: tile overlap of the split")
     ap.add_argument("--scene-batch", type=int, default=8, help="with --scene-dir: tiles per detector call")
+    ap.add_argument("--scene-tta", action="store_true",
+                    help="with --scene-dir: TEST.AUG test-time augmentation on every tile (OneStageRCNNWithTTA.detect_scenes; the "
+                         "released DOTA route: split_dota.py, do_test_with_TTA per tile, mergebypoly)")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides")
     return ap.parse_args(argv)
 
@@ -110,12 +113,14 @@ def write_synthetic_tiles(root, n, h, w, seed):
 
 def scene_args_error(args):
     """The message --scene-dir refuses a combination with, or None."""
+    if args.scene_tta and not args.scene_dir:
+        return "--scene-tta needs --scene-dir (it augments the tiles of whole scenes; --tta takes --image-dir)"
     if not args.scene_dir:
         return None
     if args.num_gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return "--scene-dir runs on one GPU: sharding scenes over several GPUs is not supported"
     if args.tta or args.tta_shard_views:
-        return "--scene-dir does not support --tta: scene-level test-time augmentation is not supported"
+        return "--scene-dir does not support --tta: use --scene-dir --scene-tta for scene-level test-time augmentation"
     return None
 
 
@@ -162,7 +167,12 @@ def run_scenes(args):
     with ThreadPoolExecutor(workers) as pool:
         imgs = list(pool.map(lambda r: read_image(r["file_name"], cfg.INPUT.FORMAT), records))
     scenes = [torch.from_numpy(a).to(dev) for a in imgs]
-    res = model.detect_scenes(scenes, patch_size=args.patch_size, overlap=args.overlap, batch=args.scene_batch)
+    if args.scene_tta:
+        from dafne_amd.modeling.tta import OneStageRCNNWithTTA
+        runner = OneStageRCNNWithTTA(cfg, model)
+    else:
+        runner = model
+    res = runner.detect_scenes(scenes, patch_size=args.patch_size, overlap=args.overlap, batch=args.scene_batch)
     names = [r["image_id"] for r in records]
     classnames = (list(de.CLASSNAMES_DOTA_1_0) + ["container-crane"])[:cfg.MODEL.DAFNE.NUM_CLASSES]
     out = args.task1_merged_dir or os.path.join(cfg.OUTPUT_DIR, "scenes")
