@@ -157,6 +157,10 @@ SIGNATURES = {
     "dafne_scene_views_u8_hip": (c_int, [ctypes.POINTER(ViewSrc), c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dafne_tta_candidates_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dafne_tta_candidates_hip": (c_int, [ctypes.POINTER(TtaView), c_int, c_int, c_int, c_int] + [c_void_p] * 10 + [c_size_t, c_void_p]),
+    "dafne_scene_match_hip": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dafne_scene_mark_workspace_bytes": (c_size_t, [c_int]),
+    "dafne_scene_mark_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_double,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

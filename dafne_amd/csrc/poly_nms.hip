@@ -2047,3 +2047,179 @@ int dafne_scene_merge_rows_hip(const float* d_rows, const int32_t* d_counts, int
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------ scene scoring (VOC matching against scene labels)
+// dafne/evaluation/voc_eval.py:132-205 for fixed inputs, on the device.  Which ground-truth box a detection matches (the
+// lowest-index maximum of iou_poly over the boxes that pass the hull test) does not depend on the greedy marking's state, so
+// the match runs per detection in parallel, and "already claimed" becomes "another detection with the same match and a
+// smaller sorted rank exists": an integer atomicMin per ground-truth box, whose result does not depend on arrival order.
+namespace {
+
+// voc_eval.py:150-178 in its own operation order: +1 on widths, heights and both areas (NOT hulls_overlap_strict)
+struct Hull {
+    double x0, y0, x1, y1;
+};
+
+__device__ __forceinline__ Hull quad_hull(const Quad& q) {
+    Hull h;
+    h.x0 = fmin(fmin(q.v[0].x, q.v[1].x), fmin(q.v[2].x, q.v[3].x));
+    h.x1 = fmax(fmax(q.v[0].x, q.v[1].x), fmax(q.v[2].x, q.v[3].x));
+    h.y0 = fmin(fmin(q.v[0].y, q.v[1].y), fmin(q.v[2].y, q.v[3].y));
+    h.y1 = fmax(fmax(q.v[0].y, q.v[1].y), fmax(q.v[2].y, q.v[3].y));
+    return h;
+}
+
+__device__ __forceinline__ bool hulls_overlap_voc(const Hull& g, const Hull& b) {
+    const double iw = fmax(fmin(g.x1, b.x1) - fmax(g.x0, b.x0) + 1.0, 0.0);
+    const double ih = fmax(fmin(g.y1, b.y1) - fmax(g.y0, b.y0) + 1.0, 0.0);
+    const double inters = iw * ih;
+    const double uni = (b.x1 - b.x0 + 1.0) * (b.y1 - b.y0 + 1.0) + (g.x1 - g.x0 + 1.0) * (g.y1 - g.y0 + 1.0) - inters;
+    return inters / uni > 0.0;
+}
+
+// One wave per detection.  Lanes stride the bucket's ground truth for the hull test (one ballot per 64 boxes); the passing
+// boxes go through iou_group16 four at a time in ascending index (group k of 16 lanes takes the k-th set bit), and the four
+// results are folded in that order with a strict `>`, so the first maximum stays (np.argmax).  Trip counts depend on the
+// ballot only: every lane reaches every iou_group16 call (it shuffles across its 16 lanes); idle groups clip the first
+// live pair again and their result is not read.
+__global__ void __launch_bounds__(64) scene_match_kernel(const double* __restrict__ dets, const int32_t* __restrict__ bucket,
+                                                         const double* __restrict__ gt, const int32_t* __restrict__ gt_offs,
+                                                         int n_buckets, int n_gt, double* __restrict__ ovmax_out,
+                                                         int32_t* __restrict__ jmax_out) {
+    __shared__ P2 lds_p[kCapP * kTile];
+    __shared__ P2 lds_pp[kCapPP * kTile];
+    const int lane = threadIdx.x;
+    const size_t d = blockIdx.x;
+    Scratch s{lds_p + lane, lds_pp + lane};
+    const Quad D = load_quad_f64(dets + d * 8);
+    const Hull hd = quad_hull(D);
+    const int b = bucket[d];
+    int g0 = 0, g1 = 0;
+    if (b >= 0 && b < n_buckets) {
+        g0 = gt_offs[b];
+        g1 = gt_offs[b + 1];
+        g0 = g0 < 0 ? 0 : (g0 > n_gt ? n_gt : g0);
+        g1 = g1 < g0 ? g0 : (g1 > n_gt ? n_gt : g1);
+    }
+    double ovmax = -HUGE_VAL;
+    int jmax = -1;
+    const int grp = lane >> 4;
+    for (int base = g0; base < g1; base += kTile) {
+        const int g = base + lane;
+        bool pass = false;
+        if (g < g1) pass = hulls_overlap_voc(quad_hull(load_quad_f64(gt + (size_t)g * 8)), hd);
+        u64 m = __ballot(pass);
+        while (m) {
+            const int cnt = __popcll(m);
+            const int pos = grp < cnt ? kth_set_bit(m, grp) : __ffsll((long long)m) - 1;
+            const int gi = base + pos;
+            const double iou = iou_group16(s, load_quad_f64(gt + (size_t)gi * 8), D, lane);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const double v = __shfl(iou, 16 * k, 64);
+                const int j = __shfl(gi, 16 * k, 64);
+                if (k < cnt && v > ovmax) {
+                    ovmax = v;
+                    jmax = j - g0;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) m &= m - 1ull;       // the four lowest bits are done (0 & anything stays 0)
+        }
+    }
+    if (lane == 0) {
+        ovmax_out[d] = ovmax;
+        jmax_out[d] = jmax;
+    }
+}
+
+__device__ __forceinline__ int match_gt_index(const int32_t* bucket, const int32_t* gt_offs, int n_buckets, int n_gt, int d, int j) {
+    const int b = bucket[d];
+    if (j < 0 || b < 0 || b >= n_buckets) return -1;
+    const int g0 = gt_offs[b], g1 = gt_offs[b + 1];
+    const long long g = (long long)g0 + j;
+    return (g0 >= 0 && g < g1 && g < n_gt) ? (int)g : -1;
+}
+
+__global__ void __launch_bounds__(256) scene_mark_init_kernel(int32_t* __restrict__ first, int n_gt) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < n_gt) first[g] = INT32_MAX;
+}
+
+// first[g] = the smallest rank among the detections matched to the non-difficult box g above the threshold
+__global__ void __launch_bounds__(256) scene_mark_claim_kernel(const int32_t* __restrict__ rank, const double* __restrict__ ovmax,
+                                                               const int32_t* __restrict__ jmax, const int32_t* __restrict__ bucket,
+                                                               int n, const int32_t* __restrict__ gt_offs, int n_buckets,
+                                                               const uint8_t* __restrict__ difficult, int n_gt, double thresh,
+                                                               int32_t* __restrict__ first) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n || !(ovmax[d] > thresh)) return;
+    const int g = match_gt_index(bucket, gt_offs, n_buckets, n_gt, d, jmax[d]);
+    if (g >= 0 && !difficult[g]) atomicMin(&first[g], rank[d]);
+}
+
+__global__ void __launch_bounds__(256) scene_mark_flag_kernel(const int32_t* __restrict__ rank, const double* __restrict__ ovmax,
+                                                              const int32_t* __restrict__ jmax, const int32_t* __restrict__ bucket,
+                                                              int n, const int32_t* __restrict__ gt_offs, int n_buckets,
+                                                              const uint8_t* __restrict__ difficult, int n_gt, double thresh,
+                                                              const int32_t* __restrict__ first, uint8_t* __restrict__ tp,
+                                                              uint8_t* __restrict__ fp) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n) return;
+    uint8_t t = 0, f = 1;                       // ovmax <= thresh (or no candidate): fp
+    const int g = ovmax[d] > thresh ? match_gt_index(bucket, gt_offs, n_buckets, n_gt, d, jmax[d]) : -1;
+    if (g >= 0) {
+        t = !difficult[g] && first[g] == rank[d];
+        f = !difficult[g] && !t;                // on a difficult box: neither
+    }
+    tp[d] = t;
+    fp[d] = f;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dafne_scene_match_hip(const double* d_dets, const int32_t* d_bucket, int n, const double* d_gt, const int32_t* d_gt_offsets,
+                          int n_buckets, int n_gt, double* d_ovmax, int32_t* d_jmax, void* stream) {
+    if (n < 0 || n_gt < 0 || n_buckets < 0) return dafne::fail(DAFNE_E_INVALID, "scene_match: bad sizes (n %d, n_gt %d, n_buckets %d)", n, n_gt, n_buckets);
+    if (n == 0) return DAFNE_OK;
+    if (!d_dets || !d_bucket || !d_ovmax || !d_jmax || (n_buckets > 0 && !d_gt_offsets) || (n_gt > 0 && !d_gt))
+        return dafne::fail(DAFNE_E_INVALID, "scene_match: null pointer");
+    hipLaunchKernelGGL(scene_match_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, d_dets, d_bucket, d_gt, d_gt_offsets,
+                       d_gt_offsets ? n_buckets : 0, n_gt, d_ovmax, d_jmax);
+    return dafne::check_launch("scene_match");
+}
+
+size_t dafne_scene_mark_workspace_bytes(int n_gt) {
+    return dafne::align_up(sizeof(int32_t) * (size_t)(n_gt > 0 ? n_gt : 1), 256);
+}
+
+int dafne_scene_mark_hip(const int32_t* d_rank, const double* d_ovmax, const int32_t* d_jmax, const int32_t* d_bucket, int n,
+                         const int32_t* d_gt_offsets, int n_buckets, const uint8_t* d_difficult, int n_gt, double thresh,
+                         uint8_t* d_tp, uint8_t* d_fp, void* d_ws, size_t ws_bytes, void* stream) {
+    if (n < 0 || n_gt < 0 || n_buckets < 0) return dafne::fail(DAFNE_E_INVALID, "scene_mark: bad sizes (n %d, n_gt %d, n_buckets %d)", n, n_gt, n_buckets);
+    if (n == 0) return DAFNE_OK;
+    if (!d_rank || !d_ovmax || !d_jmax || !d_bucket || !d_tp || !d_fp || !d_ws || (n_buckets > 0 && !d_gt_offsets) ||
+        (n_gt > 0 && !d_difficult))
+        return dafne::fail(DAFNE_E_INVALID, "scene_mark: null pointer");
+    if (ws_bytes < dafne_scene_mark_workspace_bytes(n_gt))
+        return dafne::fail(DAFNE_E_WORKSPACE, "scene_mark: workspace %zu < %zu", ws_bytes, dafne_scene_mark_workspace_bytes(n_gt));
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* first = (int32_t*)d_ws;
+    const int nbk = d_gt_offsets ? n_buckets : 0;
+    const int grid = (n + 255) / 256;
+    int rc;
+    if (n_gt > 0) {
+        hipLaunchKernelGGL(scene_mark_init_kernel, dim3((n_gt + 255) / 256), dim3(256), 0, st, first, n_gt);
+        if ((rc = dafne::check_launch("scene_mark_init"))) return rc;
+        hipLaunchKernelGGL(scene_mark_claim_kernel, dim3(grid), dim3(256), 0, st, d_rank, d_ovmax, d_jmax, d_bucket, n, d_gt_offsets,
+                           nbk, d_difficult, n_gt, thresh, first);
+        if ((rc = dafne::check_launch("scene_mark_claim"))) return rc;
+    }
+    hipLaunchKernelGGL(scene_mark_flag_kernel, dim3(grid), dim3(256), 0, st, d_rank, d_ovmax, d_jmax, d_bucket, n, d_gt_offsets, nbk,
+                       d_difficult, n_gt, thresh, first, d_tp, d_fp);
+    return dafne::check_launch("scene_mark_flag");
+}
+
+}  // extern "C"

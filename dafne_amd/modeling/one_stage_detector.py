@@ -561,6 +561,13 @@ class OneStageDetector(nn.Module):
         from .. import scene
         return scene.detect_scenes(self, scenes, patch_size=patch_size, overlap=overlap, batch=batch, layout_hwc=layout_hwc)
 
+    def score_scenes(self, results, labels, classnames, output_folder=None):
+        """detect_scenes' results against the scenes' labelTxt (evaluation.scene_eval.load_scene_labels), matched on the device:
+        VOC07 AP per class at TEST.IOU_TH, {"task1": {class: ap, ..., "map": mean}} as score_task1 gives for the same
+        detections written with write_task1_merged (evaluation/scene_eval.py, score_scenes)."""
+        from ..evaluation import scene_eval
+        return scene_eval.score_scenes(results, labels, classnames, self.cfg, output_folder=output_folder)
+
     @staticmethod
     def _enqueue_eager(plans, cs, sp, splits, defer):
         """Launch j of every sub-batch before launch j + 1; defer: an event per stream where its head begins."""

@@ -475,5 +475,9 @@ class OneStageRCNNWithTTA(nn.Module):
         from .. import scene
         return scene.detect_scenes_tta(self, scenes, patch_size=patch_size, overlap=overlap, batch=batch, layout_hwc=layout_hwc)
 
+    def score_scenes(self, results, labels, classnames, output_folder=None):
+        """OneStageDetector.score_scenes for this wrapper's detect_scenes results."""
+        return self.model.score_scenes(results, labels, classnames, output_folder=output_folder)
+
     def _merge_detections(self, instances):
         return self.model.proposal_generator.dafne_outputs.select_over_all_levels([instances])[0]

@@ -627,6 +627,31 @@ int dafne_tta_candidates_hip(const dafne_tta_view* views, int n_views, int n_ima
                              float* d_scores, float* d_ctr, int32_t* d_classes, float* d_locs, int32_t* d_levels,
                              float* d_hbox, int32_t* d_counts, int32_t* d_overflow, void* d_ws, size_t ws_bytes, void* stream);
 
+/*
+ * Scoring whole-scene detections against the scenes' labels: dafne/evaluation/voc_eval.py:132-205 for fixed inputs, without
+ * the text files.  Buckets are (scene, class): bucket s * n_classes + c.  Ground truth d_gt [n_gt, 8] f64 is sorted
+ * bucket-major (file order inside a bucket), bucket b = rows d_gt_offsets[b] .. d_gt_offsets[b + 1] (n_buckets + 1 int32).
+ *
+ * dafne_scene_match_hip: for detection d (d_dets [n, 8] f64, d_bucket [n] int32; a bucket outside [0, n_buckets) has no
+ * ground truth) the candidates are its bucket's boxes whose axis-aligned hulls pass inters / uni > 0 with the +1 convention
+ * on widths, heights and both areas (voc_eval.py:150-178, fp64, that operation order); ov = iou_poly(ground truth,
+ * detection), bit for bit polyiou.cpp.  d_ovmax[d] = max over the candidates, d_jmax[d] = the lowest index INSIDE THE
+ * BUCKET among the maxima (np.argmax); no candidates: -inf and -1.  A candidate pair that does not touch gives 0.
+ *
+ * dafne_scene_mark_hip: the greedy marking as a rank minimum.  d_rank [n] int32: the detection's position in the order
+ * voc_eval walks (descending score), distinct among the detections of one class.  With ovmax > thresh: matched box
+ * difficult (d_difficult [n_gt] uint8) -> tp = fp = 0; else tp = 1 for the smallest rank matched to that box and fp = 1 for
+ * the others; ovmax <= thresh -> fp = 1.  d_tp, d_fp [n] uint8.  d_ws: dafne_scene_mark_workspace_bytes(n_gt) bytes (one
+ * int32 per box, an integer atomicMin: its result does not depend on the order of arrival).
+ * n = 0 launches nothing; n_gt = 0 and empty buckets are valid.
+ */
+int dafne_scene_match_hip(const double* d_dets, const int32_t* d_bucket, int n, const double* d_gt, const int32_t* d_gt_offsets,
+                          int n_buckets, int n_gt, double* d_ovmax, int32_t* d_jmax, void* stream);
+size_t dafne_scene_mark_workspace_bytes(int n_gt);
+int dafne_scene_mark_hip(const int32_t* d_rank, const double* d_ovmax, const int32_t* d_jmax, const int32_t* d_bucket, int n,
+                         const int32_t* d_gt_offsets, int n_buckets, const uint8_t* d_difficult, int n_gt, double thresh,
+                         uint8_t* d_tp, uint8_t* d_fp, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,17 @@ merge_scenes.  Alternates the two --rounds times (median tiles/s of each, their 
 view launches against the gather_tiles + per-view resize_u8 calls they replace.  --out writes the JSON line to a file too.
 
     python scripts/scene_bench.py --tta --scenes 4 --batch 8 --rounds 5 --warmup 1 --out profiles/scene_tta_bench.json
+
+--score: scoring merged scene detections against scene labels, no detector involved -- synthetic merged results and labelTxt
+files of val-like size (--score-scenes scenes of 1000 .. 5000 px, 16 classes, about --score-dets detections and --score-gt
+ground-truth boxes, 70 % of both in two dense classes, scene sizes skewed) timed both ways on the same inputs: the file route
+(scene.write_task1_merged + evaluation.task1.score_task1) and evaluation.scene_eval (load_scene_labels + score_scenes),
+alternating after one untimed warm-up of each, every timing ending in a device synchronise; five repeats of score_scenes,
+five of the file route or three if one of them takes more than a minute.  Prints median / min / max of both, whether the two
+dicts are equal (as run, and with voc_eval's argsort made stable: the synthetic scores tie), and the time detect_scenes needs for scenes of these sizes (their tile count from split_origins over the
+tiles/s recorded in profiles/scene_bench.json).
+
+    python scripts/scene_bench.py --score --out profiles/scene_score_bench.json
 """
 import argparse
 import json
@@ -35,7 +46,13 @@ def main():
     ap.add_argument("--tta", action="store_true", help="scene-level TTA against the per-tile TTA route")
     ap.add_argument("--out", default="", help="also write the JSON line to this file")
     ap.add_argument("--views-per-call", type=int, default=0, help="--tta: views per detector call (0: the library's default)")
+    ap.add_argument("--score", action="store_true", help="score_scenes against write_task1_merged + score_task1 on synthetic results")
+    ap.add_argument("--score-scenes", type=int, default=400)
+    ap.add_argument("--score-dets", type=int, default=200000)
+    ap.add_argument("--score-gt", type=int, default=50000)
     args = ap.parse_args()
+    if args.score:
+        return bench_score(args)
     import torch
     import bench
     import dafne_amd.modeling  # noqa: F401
@@ -196,6 +213,147 @@ def bench_tta(args, cfg, m, scenes, origins, info, tiles):
         "batch_gather_resize_ms_median": round(statistics.median(resize_ms), 3),
         "merged_detections": int(sum(len(r["scores"]) for r in res)),
         "s_tile_route": [round(v, 4) for v in t_tile], "s_scene": [round(v, 4) for v in t_scene]})
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def _boxes(rng, n, size, lo, hi):
+    """n rotated rectangles inside a size x size scene, [n,8] float64."""
+    import numpy as np
+    c = rng.uniform(0, size, (n, 2))
+    w = np.exp(rng.uniform(np.log(lo), np.log(hi), n))
+    h = w / rng.uniform(1, 4, n)
+    a = rng.uniform(0, np.pi, n)
+    ca, sa = np.cos(a), np.sin(a)
+    ux = np.stack([w / 2 * ca - h / 2 * sa, -w / 2 * ca - h / 2 * sa, -w / 2 * ca + h / 2 * sa, w / 2 * ca + h / 2 * sa], 1)
+    uy = np.stack([w / 2 * sa + h / 2 * ca, -w / 2 * sa + h / 2 * ca, -w / 2 * sa - h / 2 * ca, w / 2 * sa - h / 2 * ca], 1)
+    p = np.empty((n, 8))
+    p[:, 0::2] = c[:, :1] + ux
+    p[:, 1::2] = c[:, 1:] + uy
+    return p
+
+
+def synthetic_val(args, label_dir):
+    """Seeded merged results + labelTxt files of val-like size.  -> scene names, class names, scene sizes, per-scene host
+    results (corners two decimals, scores four decimals: many equal scores, as real merged files have)."""
+    import numpy as np
+    from dafne_amd.evaluation import dota_evaluation as de
+    rng = np.random.default_rng(7)
+    classes = list(de.CLASSNAMES_DOTA_1_0) + ["container-crane"]
+    S, C = args.score_scenes, len(classes)
+    sizes = rng.choice([1000, 2000, 3000, 4000, 5000], S, p=[0.15, 0.2, 0.25, 0.3, 0.1])
+    share = np.full(C, 0.3 / (C - 2))
+    share[[4, 5]] = 0.35                                          # small-vehicle, large-vehicle
+    weight = rng.lognormal(0.0, 1.2, (S, C)) * share[None, :] * (sizes[:, None] / 4000.0) ** 2     # a few scenes hold most boxes
+    n_gt = rng.poisson(weight / weight.sum() * args.score_gt)
+    n_fp = rng.poisson(weight / weight.sum() * (args.score_dets - 1.15 * args.score_gt))
+    names, results = [], []
+    os.makedirs(label_dir, exist_ok=True)
+    for s in range(S):
+        name = "P%04d" % s
+        names.append(name)
+        rows = ["imagesource:GoogleEarth", "gsd:0.146"]
+        corners, labels = [], []
+        for c in range(C):
+            lo, hi = (10.0, 40.0) if c in (4, 5) else (20.0, 150.0)
+            g = np.round(_boxes(rng, int(n_gt[s, c]), float(sizes[s]), lo, hi), 1)
+            diff = rng.uniform(size=len(g)) < 0.1
+            rows += [" ".join("%.1f" % v for v in q) + " %s %d" % (classes[c], d) for q, d in zip(g, diff)]
+            first = g[rng.uniform(size=len(g)) < 0.85]
+            second = g[rng.uniform(size=len(g)) < 0.3]
+            d = np.concatenate([first + rng.normal(0, 1.0, first.shape), second + rng.normal(0, 2.0, second.shape),
+                                _boxes(rng, int(n_fp[s, c]), float(sizes[s]), lo, hi)])
+            corners.append(np.round(d, 2))
+            labels.append(np.full(len(d), c, np.int64))
+        with open(os.path.join(label_dir, name + ".txt"), "w") as f:
+            f.write("\n".join(rows) + "\n")
+        corners, labels = np.concatenate(corners), np.concatenate(labels)
+        results.append((corners, np.round(rng.uniform(0.05, 1.0, len(labels)), 4), labels))
+    return names, classes, sizes, results
+
+
+def bench_score(args):
+    import tempfile
+    import types
+    import numpy as np
+    import torch
+    from dafne_amd import scene as sc
+    from dafne_amd.evaluation import dota_evaluation as de
+    from dafne_amd.evaluation.scene_eval import load_scene_labels, score_scenes
+    from dafne_amd.evaluation.task1 import score_task1
+    dev = torch.device("cuda", 0)
+    cfg = types.SimpleNamespace(TEST=types.SimpleNamespace(IOU_TH=0.5))
+    with tempfile.TemporaryDirectory() as tmp:
+        label_dir = os.path.join(tmp, "labelTxt")
+        names, classes, sizes, host = synthetic_val(args, label_dir)
+        res = [{"corners": torch.from_numpy(c).to(dev), "scores": torch.from_numpy(s).to(dev), "labels": torch.from_numpy(l).to(dev)}
+               for c, s, l in host]
+        n_det = sum(len(l) for _, _, l in host)
+        out = os.path.join(tmp, "files")
+        os.makedirs(out)
+        with open(os.path.join(out, "imageset.txt"), "w") as f:
+            f.write("\n".join(names))
+        last = {}
+
+        def file_route():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            merged = os.path.join(out, "Task1_merged")
+            sc.write_task1_merged(res, names, classes, merged)
+            last["file"] = score_task1(classes, merged, os.path.join(label_dir, "{:s}.txt"), out, de.parse_gt, cfg, {})
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+        def device_route():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lab = load_scene_labels(label_dir, names, classes)
+            t1 = time.perf_counter()
+            last["dev"] = score_scenes(res, lab, classes, cfg, output_folder=os.path.join(tmp, "dev"))
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            last["labels_s"], last["gt"] = t1 - t0, int(lab["boxes"].shape[0])
+            return t2 - t0
+
+        w_file, w_dev = file_route(), device_route()              # untimed warm-up of each
+        print("warm-up: file route %.2f s, score_scenes %.3f s" % (w_file, w_dev), flush=True)
+        n_file = 3 if w_file > 60.0 else 5
+        t_file, t_dev, t_lab = [], [], []
+        for r in range(5):
+            if r < n_file:
+                t_file.append(file_route())
+                if t_file[-1] > 60.0:
+                    n_file = 3
+            t_dev.append(device_route())
+            t_lab.append(last["labels_s"])
+            print("repeat %d: file route %s s, score_scenes %.3f s" % (r, ("%.2f" % t_file[-1]) if r < len(t_file) else "-", t_dev[-1]),
+                  flush=True)
+        # equal scores: numpy's unstable argsort may order them differently from the stable order score_scenes defines, so the
+        # two dicts are compared once more (untimed) with voc_eval's argsort in its kind="stable" form
+        same = list(last["file"].items()) == list(last["dev"]["task1"].items())
+        plain = np.argsort
+        np.argsort = lambda a, *x, **k: plain(a, kind="stable")
+        try:
+            stable = score_task1(classes, os.path.join(out, "Task1_merged"), os.path.join(label_dir, "{:s}.txt"), out, de.parse_gt, cfg, {})
+        finally:
+            np.argsort = plain
+        same_stable = list(stable.items()) == list(last["dev"]["task1"].items())
+        tiles = int(sum(len(sc.split_origins(int(v), int(v))) for v in sizes))
+        with open(os.path.join(ROOT, "profiles", "scene_bench.json")) as f:
+            rate = float(json.loads(f.read())["tiles_per_s_detect_scenes"])
+        line = json.dumps({
+            "scenes": len(names), "classes": len(classes), "detections": n_det, "gt_boxes": last["gt"], "tiles": tiles,
+            "file_route_s": {"median": round(statistics.median(t_file), 3), "min": round(min(t_file), 3), "max": round(max(t_file), 3)},
+            "score_scenes_s": {"median": round(statistics.median(t_dev), 4), "min": round(min(t_dev), 4), "max": round(max(t_dev), 4)},
+            "of_which_load_scene_labels_s_median": round(statistics.median(t_lab), 4),
+            "ratio_of_medians": round(statistics.median(t_file) / statistics.median(t_dev), 1),
+            "detect_scenes_s_for_these_tiles": round(tiles / rate, 2), "tiles_per_s_detect_scenes_recorded": rate,
+            "slowest_score_scenes_faster_than_fastest_file_route": bool(max(t_dev) < min(t_file)),
+            "score_scenes_median_below_detect_scenes": bool(statistics.median(t_dev) < tiles / rate),
+            "task1_dicts_equal": bool(same), "task1_dicts_equal_with_stable_argsort": bool(same_stable), "map_file_route": last["file"]["map"], "map_score_scenes": last["dev"]["task1"]["map"],
+            "s_file_route": [round(v, 3) for v in t_file], "s_score_scenes": [round(v, 4) for v in t_dev]})
     print(line)
     if args.out:
         with open(args.out, "w") as f:

@@ -79,6 +79,10 @@ def parse_args(argv=None):
     ap.add_argument("--scene-tta", action="store_true",
                     help="with --scene-dir: TEST.AUG test-time augmentation on every tile (OneStageRCNNWithTTA.detect_scenes; the "
                          "released DOTA route: split_dota.py, do_test_with_TTA per tile, mergebypoly)")
+    ap.add_argument("--scene-labels", default="",
+                    help="with --scene-dir: the scenes' labelTxt directory (<scene>.txt per scene, the val split): score the merged "
+                         "detections against them on the device (VOC07 AP per class at TEST.IOU_TH), print the table and write "
+                         "results.txt beside Task1_merged/")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides")
     return ap.parse_args(argv)
 
@@ -115,6 +119,8 @@ def scene_args_error(args):
     """The message --scene-dir refuses a combination with, or None."""
     if args.scene_tta and not args.scene_dir:
         return "--scene-tta needs --scene-dir (it augments the tiles of whole scenes; --tta takes --image-dir)"
+    if args.scene_labels and not args.scene_dir:
+        return "--scene-labels needs --scene-dir (it scores whole-scene detections; --dataset-name scores tile detections)"
     if not args.scene_dir:
         return None
     if args.num_gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -135,7 +141,8 @@ def write_zip(output_dir, merged_dir):
 
 def run_scenes(args):
     """--scene-dir: every image file of the directory is one scene (decoded on host workers with read_image, BGR HWC), all of
-    them go through ONE detect_scenes call; Task1_merged/ as mergebypoly writes it for the same scenes split into tiles."""
+    them go through ONE detect_scenes call; Task1_merged/ as mergebypoly writes it for the same scenes split into tiles.  With
+    --scene-labels the results are scored against the scenes' labelTxt on the device (evaluation/scene_eval.py) -> results.txt."""
     from concurrent.futures import ThreadPoolExecutor
     import dafne_amd.modeling  # noqa: F401
     from dafne_amd.checkpoint import load_weights
@@ -185,6 +192,13 @@ def run_scenes(args):
     for n, r, s in zip(names, res, scenes):
         print("scene %s (%dx%d, %d tiles): %d detections" % (n, s.shape[0], s.shape[1], len(r["origins"]), len(r["scores"])))
     print("Task1_merged written to %s" % merged)
+    if args.scene_labels:
+        from dafne_amd.evaluation.scene_eval import load_scene_labels
+        labels = load_scene_labels(args.scene_labels, names, classnames)
+        scored = runner.score_scenes(res, labels, classnames, output_folder=out)
+        for k, v in scored["task1"].items():
+            print(f"{k: <18}: {v:2.4f}")
+        print("results.txt written to %s" % out)
     return res
 
 
