@@ -3676,6 +3676,8 @@ bool rp_shape_ok(const dafne_conv_params* p, const dafne_conv_seg* segs) {
     return true;
 }
 
+bool stream_eligible(const ConvDev& D);
+
 int build(ConvDev& D, const dafne_conv_params* p, const dafne_conv_seg* segs, bool fp8 = false, bool rp = false) {
     if (!p || !segs) return dafne::fail(DAFNE_E_INVALID, "conv: null params");
     D.oscale = nullptr;
@@ -3777,6 +3779,13 @@ int build(ConvDev& D, const dafne_conv_params* p, const dafne_conv_seg* segs, bo
         }
         if ((long long)g.Hout * g.Wout > (1 << 20) || g.Wout > (1 << 12))
             return dafne::fail(DAFNE_E_UNSUPPORTED, "conv: segment %d output %dx%d above 2^20 pixels per image", s, g.Hout, g.Wout);
+        // the kernels address the input of a segment (image index included) with 32-bit byte offsets: the whole haloed map,
+        // every tap of the last pixel of the last image with it, must lie below 2^32
+        const long long in_bytes = stem ? (long long)p->n_images * g.Hin * g.Win * 8
+                                        : (long long)p->n_images * (g.Hin + 2) * (g.Win + 2) * p->Cin * 2;
+        if (in_bytes > 0xffffffffll)
+            return dafne::fail(DAFNE_E_UNSUPPORTED, "conv: segment %d input of %lld bytes (%d images of %dx%dx%d) is beyond 32-bit offsets: "
+                                                    "split the batch", s, in_bytes, p->n_images, g.Hin, g.Win, p->Cin);
         SegDev& o = D.seg[s];
         o.in = (const char*)g.d_in; o.out = (char*)g.d_out; o.res = (const char*)g.d_res;
         o.Hin = g.Hin; o.Win = g.Win; o.Hout = g.Hout; o.Wout = g.Wout;
@@ -3788,6 +3797,16 @@ int build(ConvDev& D, const dafne_conv_params* p, const dafne_conv_seg* segs, bo
     }
     D.mtiles = t;
     D.ntiles = D.Cout_pad / c.bn;
+    if ((long long)D.Cout_pad * D.kbytes > 0xffffffffll)
+        return dafne::fail(DAFNE_E_UNSUPPORTED, "conv: weights of %lld bytes are beyond 32-bit offsets", (long long)D.Cout_pad * D.kbytes);
+    // conv_stream_kernel fetches its residual tile with 32-bit byte offsets as well (the other kernels use 64-bit ones there)
+    if ((p->flags & DAFNE_CONV_RESIDUAL) && !D.patch && !D.slab && !D.rp && stream_eligible(D))
+        for (int s = 0; s < p->n_segs; s++) {
+            const long long res_bytes = (long long)p->n_images * (segs[s].Hout + 2) * (segs[s].Wout + 2) * p->Cout * 2;
+            if (res_bytes > 0xffffffffll)
+                return dafne::fail(DAFNE_E_UNSUPPORTED, "conv: segment %d residual of %lld bytes (%d images of %dx%dx%d) is beyond 32-bit "
+                                                        "offsets: split the batch", s, res_bytes, p->n_images, segs[s].Hout, segs[s].Wout, p->Cout);
+        }
     return DAFNE_OK;
 }
 

@@ -448,7 +448,10 @@ class ConvCall:
             return "conv3x3_patch_fp8"
         if self.wfrag is not None:
             return "conv3x3_rp"
-        return self.KERNEL_NAMES[self.kernel_id()]
+        kid = self.kernel_id()
+        if kid < 0:                # (never KERNEL_NAMES[-1]: a call the library refuses has no kernel)
+            _lib.check(kid, "dafne_conv2d_kernel_id")
+        return self.KERNEL_NAMES[kid]
 
     def tiles_per_image(self):
         out = (ctypes.c_int32 * self.prm.n_segs)()
@@ -1087,6 +1090,9 @@ class HeadPlan:
                 # uses the patch kernel's tiles, the bf16 one only when the launch has enough of them)
                 probe = ConvCall(wgt, bias, C, C, 3, 1, 1, flags & ~F_GN, seg_list(cur, outs), n, gn_in=cur_gn, shared_gpu=sg)
                 rp_on = use_rp_kernel() and C == 256
+                if probe.kernel_id() < 0 and not (rp_on and probe.rp_ok()):
+                    probe.kernel_name()            # refused (e.g. a batch beyond 32-bit offsets): raise the library's message
+                                                   # here, not a tile count of -1 further down
                 use_fp8 = q8 is not None and aq is not None and (cur_gn is None or probe.kernel_id() == 6 or (rp_on and probe.rp_ok()))
                 # (the FPN-fed layer 0 of a SMALL plan -- the 2-image sub-batch of the timed layout -- takes the generic tile, kernel
                 # id != 6, and is then followed by ONE dafne_groupnorm_finalize_hip launch per tower: the two gn_finalize launches

@@ -250,6 +250,10 @@ typedef struct dafne_conv_params {
  * ResNet stem as (Cin=4, 7x7, stride 2) on the image layout that
  * dafne_preprocess_image_hip writes (K = 7 rows x 8 cols x 4 ch, zero weights in
  * the padding taps; weight rows are 256 bf16).
+ * Limits per segment (DAFNE_E_UNSUPPORTED beyond them): 2^20 output pixels per image; 2^32 - 1
+ * bytes of haloed input over all images, n_images * (Hin+2) * (Win+2) * Cin * 2 (the kernels use
+ * 32-bit byte offsets that include the image index), and as many bytes of residual on the
+ * streaming 1x1 kernel: split a larger batch.
  */
 int dafne_conv2d_nhwc_bf16_hip(const dafne_conv_params* prm, const dafne_conv_seg* segs, void* stream);
 /*

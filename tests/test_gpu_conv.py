@@ -72,9 +72,12 @@ CASES = [
     (256, 256, 3, 2, 1, 16, 16, 1),     # P6/P7
     (512, 2048, 1, 1, 0, 4, 4, 1),
     (1024, 256, 1, 1, 0, 8, 8, 1),
-    (64, 256, 1, 1, 0, 256, 256, 2),    # >= 512 blocks of 256x256: the 8-wave tile
-    (64, 512, 3, 1, 1, 120, 150, 2),    # 8-wave tile, ragged, two N tiles
+    (64, 256, 1, 1, 0, 256, 256, 2),    # 1 024 tiles of 128 px on the weight-stationary kernel (Cin <= 256 never takes the 8-wave tile)
+    (64, 512, 3, 1, 1, 120, 150, 2),    # the 3x3 patch kernel: ragged 8 x 32 tiles, two channel tiles
 ]
+# the kernel each of them runs on (tests/_conv_cases.py holds the per-kernel table; tests/test_conv_dispatch_cpu.py pins it)
+CASE_KERNELS = ["conv_igemm<1,4,2,2>", "conv_ws", "conv_ws", "conv_igemm<1,4,2,2>", "conv_igemm<2,2,2,2>", "conv_igemm<2,2,2,2>",
+                "conv_igemm<2,2,2,2>", "conv_stream", "conv_igemm<2,2,2,2>", "conv_ws", "conv3x3_patch"]
 
 
 @pytest.mark.parametrize("cin,cout,k,stride,pad,H,W,N", CASES)
@@ -84,7 +87,8 @@ def test_conv_vs_torch(cin, cout, k, stride, pad, H, W, N):
     w = bfr(torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5)
     b = torch.randn(cout, generator=g) * 0.1
     ref = bfr(F.conv2d(x, w, b, stride=stride, padding=pad))
-    got, _, _ = run_conv(x, w, b, k, stride, pad)
+    got, _, call = run_conv(x, w, b, k, stride, pad)
+    assert call.kernel_name() == CASE_KERNELS[CASES.index((cin, cout, k, stride, pad, H, W, N))]
     close_bf16(got, ref)
 
 
@@ -109,11 +113,12 @@ def test_conv_relu_residual_and_upsample_add():
     (64, 128, 97, 113, 3, True, False),      # H = 2 half-K stages per tile (shortest K), one N tile
     (256, 1024, 40, 40, 3, True, True),      # res4-conv3 shape: 8 N tiles share each pixel tile
     (64, 256, 150, 131, 2, False, True),     # no residual: staging tile is write-only
-    (1024, 256, 24, 24, 2, False, True),     # long K (32 half-K stages)
+    (1024, 256, 24, 24, 2, False, True),     # long K: Cin > 512 stays on the one-tile kernel, conv_igemm<2,2,2,2>
 ])
-def test_streaming_1x1_kernel(cin, cout, H, W, N, with_res, relu):
-    """Persistent streaming 1x1 kernel (conv.hip: conv_stream_kernel): residual DMA tile, in-place
-    epilogue, counted vmcnt waits across tile boundaries."""
+def test_ws_1x1_kernel_and_long_k_one_tile_kernel(cin, cout, H, W, N, with_res, relu):
+    """Persistent weight-stationary 1x1 kernel (conv.hip: conv_ws_kernel, Cin 64 / 128 / 256): residual DMA tile, several tiles
+    per workgroup, ragged last tile; the Cin = 1024 case is not a persistent-kernel shape and runs conv_igemm<2,2,2,2>.
+    (conv_stream_kernel, Cin 192 / 320 / 384 / 512, has its cases in tests/test_gpu_conv_matrix.py.)"""
     from dafne_amd import engine
     g = torch.Generator().manual_seed(cin + cout + H)
     x = bfr(torch.randn(N, cin, H, W, generator=g))
@@ -126,7 +131,8 @@ def test_streaming_1x1_kernel(cin, cout, H, W, N, with_res, relu):
     if relu:
         ref = F.relu(ref)
     flags = (engine.F_RELU if relu else 0) | (engine.F_RES if with_res else 0)
-    got, _, _ = run_conv(x, w, b, 1, 1, 0, flags=flags, res=res)
+    got, _, call = run_conv(x, w, b, 1, 1, 0, flags=flags, res=res)
+    assert call.kernel_name() == ("conv_ws" if cin <= 256 else "conv_igemm<2,2,2,2>")
     close_bf16(got, bfr(ref))
 
 
@@ -386,7 +392,8 @@ def test_prediction_conv_f32_output(cout):
     w = bfr(torch.randn(cout, 256, 3, 3, generator=g) / 48.0)
     b = torch.randn(cout, generator=g)
     ref = F.conv2d(x, w, b, padding=1)
-    got, _, _ = run_conv(x, w, b, 3, 1, 1, out_f32=True)
+    got, _, call = run_conv(x, w, b, 3, 1, 1, out_f32=True)
+    assert call.kernel_name() == "conv3x3_pred16"
     assert torch.isfinite(got).all()
     assert float((got - ref).abs().max()) < 2e-3 * float(ref.abs().max())
 
@@ -430,7 +437,8 @@ def test_groupnorm_relu_pipeline():
 
 
 def test_big_tile_groupnorm_stats_and_residual():
-    """256x256 tile path: GN partial sums (reduced on the host here) and residual+ReLU."""
+    """256x256 tile (conv_igemm<4,2,2,4>): GN partial sums (reduced on the host here); then the same layer with residual + ReLU,
+    which takes 128-wide tiles on conv_stream (512 tiles on 512 resident slots: one tile per workgroup)."""
     from dafne_amd import engine, _lib
     g = torch.Generator().manual_seed(6)
     N, C, H, W, CI = 2, 256, 128, 128, 320     # (1x1 layers with <= 256 input channels go to 128-wide tiles: conv_ws)
@@ -446,8 +454,9 @@ def test_big_tile_groupnorm_stats_and_residual():
     assert probe.tile_pixels() == 256
     nt = probe.num_tiles()
     partial = torch.zeros(nt, C // 8, 2, dtype=torch.float32, device=d)
-    engine.ConvCall(wp, bp, CI, C, 1, 1, 0, engine.F_GN, [(a.t, oa.t, None, H, W, H, W)], N, gn_partial=partial)(
-        _lib.current_stream())
+    gn_call = engine.ConvCall(wp, bp, CI, C, 1, 1, 0, engine.F_GN, [(a.t, oa.t, None, H, W, H, W)], N, gn_partial=partial)
+    assert gn_call.kernel_name() == "conv_igemm<4,2,2,4>"
+    gn_call(_lib.current_stream())
     torch.cuda.synchronize()
     close_bf16(oa.nchw_float().cpu(), bfr(y))
     ps = partial.cpu().reshape(N, nt // N, C // 8, 2).sum(1)
@@ -455,7 +464,8 @@ def test_big_tile_groupnorm_stats_and_residual():
     assert torch.allclose(ps[..., 0], grp.sum(-1), rtol=1e-4, atol=1e-1)
     assert torch.allclose(ps[..., 1], (grp * grp).sum(-1), rtol=1e-4, atol=1e-1)
     res = bfr(torch.randn(N, C, H, W, generator=g))
-    got, _, _ = run_conv(x, w, b, 1, 1, 0, flags=engine.F_RELU | engine.F_RES, res=res)
+    got, _, call = run_conv(x, w, b, 1, 1, 0, flags=engine.F_RELU | engine.F_RES, res=res)
+    assert call.kernel_name() == "conv_stream" and call.num_tiles() * (C // 128) == 512
     close_bf16(got, bfr(F.relu(y + res)))
 
 
