@@ -139,6 +139,8 @@ SIGNATURES = {
                                                            c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dafne_bottleneck_block_narrow_scratch_bytes": (c_size_t, []),
     "dafne_bottleneck_block_narrow_hip": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dafne_bottleneck_block_narrow_s2_scratch_bytes": (c_size_t, []),
+    "dafne_bottleneck_block_narrow_s2_hip": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dafne_bottleneck_block_mid_scratch_bytes": (c_size_t, []),
     "dafne_bottleneck_block_mid_hip": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dafne_stem_pool_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -71,7 +71,7 @@ def build(force=False, verbose=False):
 # The static ISA guards (scripts/check_async_loads.py, scripts/check_packed_fp32.py) as a BUILD step: `python -m dafne_amd.build --check`
 # compiles every unit once more to a listing (hipcc -S, same flags) and fails on a flagged instruction.  ASYNC_CHECKED: the units whose
 # hand-scheduled kernels are fully unrolled per tile, which is what the checker's in-order queue walks (program-text order); the
-# persistent kernels with RUNTIME loops (conv_b2b_mid / _narrow, conv_blk_mid / _narrow, conv_wr) re-use ring registers across a back
+# persistent kernels with RUNTIME loops (conv_b2b_mid / _narrow, conv_blk_mid / _narrow / _narrow_s2, conv_wr) re-use ring registers across a back
 # edge the model does not follow -- their waits are covered by the bit-identity tests under load (tests/test_gpu_reproducible.py).
 ASYNC_CHECKED = {"conv.hip": ["conv3x3_rp_kernel"], "conv_bneck.hip": ["conv_bneck_kernel"], "conv_b2b.hip": ["conv_b2b_kernel"],
                  "conv3x3_c64.hip": ["conv3x3_c64_kernel"]}

@@ -25,6 +25,7 @@
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -92,6 +93,10 @@ __device__ __forceinline__ void static_for(F&& f) {
 // its own step group (3 - s fragments + 2 pieces), the 6 operations of the next group and the s fragments of this step --
 // and "my pieces of stage i+1 have landed" is `vmcnt(9)` in front of sub-step 3.  Steps past the end of the slice re-load
 // the last step (dead stages / ring slots): the counts stay constant, no wait ever drains the queue.
+// RELU_IN (DAFNE_CONV_RELU_INPUT): ReLU of the INPUT applied to the pixel fragments once they are in registers -- per bf16 a set
+// sign bit gives 0 and anything else stays as it is (-0, negative NaNs and -inf included: dafne_relu_copy_bf16_hip's definition),
+// which is a signed 16-bit max with 0: one v_pk_max_i16 per dword.  An instantiation of its own: the plain kernel's schedule is untouched.
+template <bool RELU_IN>
 __global__ void __launch_bounds__(512, 2) conv_wr_kernel(WrDev P) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x;
@@ -216,6 +221,13 @@ __global__ void __launch_bounds__(512, 2) conv_wr_kernel(WrDev P) {
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
                 bread(nxt, 0, bfr[0]);
+            }
+            if constexpr (RELU_IN) {
+#pragma unroll
+                for (int b = 0; b < kPF; b++) {
+                    const s16x8 v = __builtin_bit_cast(s16x8, bfr[s & 1][b]);
+                    bfr[s & 1][b] = __builtin_bit_cast(bf16x8, __builtin_elementwise_max(v, s16x8{}));
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -350,7 +362,7 @@ __global__ void __launch_bounds__(512, 2) conv_wr_kernel(WrDev P) {
 int wr_build(WrDev& D, const dafne_conv_params* prm, const dafne_conv_seg* segs, const char** why) {
     *why = nullptr;
     if (!prm || !segs) { *why = "null argument"; return 0; }
-    const unsigned allowed = DAFNE_CONV_RELU | DAFNE_CONV_RESIDUAL | DAFNE_CONV_UPSAMPLE_ADD | DAFNE_CONV_EXCLUSIVE;
+    const unsigned allowed = DAFNE_CONV_RELU | DAFNE_CONV_RESIDUAL | DAFNE_CONV_UPSAMPLE_ADD | DAFNE_CONV_EXCLUSIVE | DAFNE_CONV_RELU_INPUT;
     if (prm->n_segs != 1) { *why = "one segment"; return 0; }
     if (prm->flags & ~allowed) { *why = "flags"; return 0; }
     if ((prm->flags & DAFNE_CONV_RESIDUAL) && (prm->flags & DAFNE_CONV_UPSAMPLE_ADD)) { *why = "residual and top-down add"; return 0; }
@@ -429,8 +441,9 @@ int dafne_conv2d_wr_hip(const dafne_conv_params* prm, const dafne_conv_seg* segs
     D.wf = (const char*)d_wfrag;
     D.counters = (int*)d_workspace;
     D.slabs = (char*)d_workspace + kCounterBytes;
-    DAFNE_MAX_LDS_ONCE(kSmemTotal, (const void*)conv_wr_kernel);
-    hipLaunchKernelGGL(conv_wr_kernel, dim3((unsigned)(tiles * D.S)), dim3(kNT), kSmemTotal, (hipStream_t)stream, D);
+    DAFNE_MAX_LDS_ONCE(kSmemTotal, (const void*)conv_wr_kernel<false>, (const void*)conv_wr_kernel<true>);
+    if (D.flags & DAFNE_CONV_RELU_INPUT) hipLaunchKernelGGL(conv_wr_kernel<true>, dim3((unsigned)(tiles * D.S)), dim3(kNT), kSmemTotal, (hipStream_t)stream, D);
+    else hipLaunchKernelGGL(conv_wr_kernel<false>, dim3((unsigned)(tiles * D.S)), dim3(kNT), kSmemTotal, (hipStream_t)stream, D);
     return dafne::check_launch("conv_wr");
 }
 

@@ -22,6 +22,9 @@ STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3)}
 
 F_RELU, F_RES, F_UP, F_F32, F_GN, F_GNIN, F_GNFIN, F_EXCL = 1, 2, 4, 8, 16, 32, 64, 128
 F_FRAG16 = 256      # dafne_conv3x3_c256_hip only: the weights are pack_conv3x3_frag16's, the launch runs the 16x16x32 form
+F_RELU_INPUT = 512  # dafne_conv2d_wr_hip only: ReLU of the input applied on load (P7 reads relu(P6) without a rectified copy)
+FPN_IN_FEATURES = ("res3", "res4", "res5")      # MODEL.FPN.IN_FEATURES of every released config: the stage outputs a plan retains
+#                                                 (the one place that says so: buffer reuse and the res2 tail both ask it)
 
 
 # ------------------------------------------------------------------ activations
@@ -668,6 +671,7 @@ class DensePlan:
                 self.calls.append(w)
                 self.flops += w.flops
                 return o
+            assert not (flags & F_RELU_INPUT), "only conv_wr rectifies its input on load (the caller checks wr_takes)"
             if fp8 is None and k == 3 and cin == 256 and use_rp_kernel() and c.kernel_id() == 6 and c.rp_ok():
                 # 256-channel 3x3 layers the patch kernel would take (FPN outputs): resident-patch kernel
                 f16 = rp_frag16()
@@ -728,6 +732,11 @@ class DensePlan:
         blk_mid_scratch = None
         fuse_blk_mid = fuse_mid and os.environ.get("DAFNE_FUSE_BLK_MID", "1") != "0"
         fuse_blk_narrow = fuse_narrow and os.environ.get("DAFNE_FUSE_BLK_NARROW", "1") != "0"
+        # the last block of a stage nobody but the next stage reads is computed only at the pixels the next stage's stride-2
+        # 1x1 layers touch (conv_blk_narrow_s2.hip); DAFNE_RES2_TAIL_S2=0: the full map (A/B runs)
+        tail_s2 = os.environ.get("DAFNE_RES2_TAIL_S2", "1") != "0"
+        blk_s2_scratch = None
+        x_compact = False         # x holds only the even pixels of the stage output: the next block 0 reads it with stride 1
         for si, nb in enumerate(STAGE_BLOCKS[depth]):
             y1_next = stem_y1 if si == 0 else None
             for b in range(nb):
@@ -739,14 +748,16 @@ class DensePlan:
                 proj_fused = (fuse_narrow and b == 0 and stride == 1 and nb > 1 and tuple(w3.shape) == (256, 64)
                               and tuple(P[p + "shortcut"][0].shape) == (256, 64) and tuple(P[nxt][0].shape) == (64, 256))
                 # (the whole-block kernel below takes block 0 under the same conditions: its projection is fused as well)
+                in_stride = 1 if (b == 0 and x_compact) else stride      # (the previous stage's tail has applied the stride)
                 if b == 0:
-                    sc = None if proj_fused else conv(p + "shortcut", x, 1, stride, 0, 0)
+                    sc = None if proj_fused else conv(p + "shortcut", x, 1, in_stride, 0, 0)
                 else:
                     sc = x
                 if y1_next is not None:
                     y1, y1_next = y1_next, None                       # computed by the previous block's fused tail
                 else:
-                    y1 = conv(p + "conv1", x, 1, stride, 0, F_RELU)       # STRIDE_IN_1X1
+                    y1 = conv(p + "conv1", x, 1, in_stride, 0, F_RELU)    # STRIDE_IN_1X1
+                x_compact = False
                 w2, b2 = P[p + "conv2"]
                 q8_2 = P.get(p + "conv2.fp8")
                 bn_head = b + 1 < nb                  # the stage's last block has no next conv1: the kernel's no-head form
@@ -779,7 +790,7 @@ class DensePlan:
                     pool.put(y1)
                     if b == 0 and sc is not None and sc is not y3:
                         pool.put(sc)
-                    if x is not y3 and not any(x is f for k, f in feats.items() if k != "res2"):
+                    if x is not y3 and not any(x is f for k, f in feats.items() if k in FPN_IN_FEATURES):
                         pool.put(x)
                     x = y3
                     continue
@@ -798,6 +809,27 @@ class DensePlan:
                     if blk_scratch is None:
                         blk_scratch = torch.empty(L.dafne_bottleneck_block_narrow_scratch_bytes(), dtype=torch.uint8, device=device)
                     src = x if proj else sc               # projection: the block input; identity: the previous block's output
+                    nx0 = "res%d.0." % (si + 3)
+                    if (tail_s2 and calib is None and not head and not proj and si + 1 < len(STAGE_BLOCKS[depth])
+                            and "res%d" % (si + 2) not in FPN_IN_FEATURES
+                            # the only readers are the next stage's two 1x1 stride-2 layers (packed 1x1 weights: [Cout, Cin])
+                            and tuple(P[nx0 + "conv1"][0].shape)[1:] == (256,) and tuple(P[nx0 + "shortcut"][0].shape)[1:] == (256,)):
+                        if blk_s2_scratch is None:
+                            blk_s2_scratch = torch.empty(L.dafne_bottleneck_block_narrow_s2_scratch_bytes(), dtype=torch.uint8, device=device)
+                        ho, wo = (y1.h + 1) // 2, (y1.w + 1) // 2
+                        y3 = pool.get(n, ho, wo, 256)
+                        fl = 2 * n * ho * wo * (64 * 576 + 64 * 256)
+                        nb_ = n * (y1.h * y1.w * 64 + ho * wo * (256 + 256)) * 2 + (64 * 576 + 256 * 64) * 2
+                        self.calls.append(FnCall(L.dafne_bottleneck_block_narrow_s2_hip,
+                                                 (_lib.ptr(y1.t), _lib.ptr(src.t), _lib.ptr(P[key]), _lib.ptr(b2), _lib.ptr(b3), n, y1.h, y1.w,
+                                                  _lib.ptr(y3.t), _lib.ptr(blk_s2_scratch), blk_s2_scratch.numel()),
+                                                 (y1, src, P[key], b2, b3, y3, blk_s2_scratch), "conv_blk_narrow_s2", flops=fl, nbytes=nb_))
+                        self.flops += fl
+                        pool.put(y1)
+                        pool.put(x)
+                        x = y3
+                        x_compact = True
+                        continue
                     inpl = (not proj) and res_dead(sc, x, b)
                     y3 = sc if inpl else pool.get(n, y1.h, y1.w, 256)
                     y1_next = pool.get(n, y1.h, y1.w, 64) if head else None
@@ -812,7 +844,7 @@ class DensePlan:
                                              "conv_blk_narrow" + ("_proj" if proj else "") + ("" if head else "_last"), flops=fl, nbytes=nb_))
                     self.flops += fl
                     pool.put(y1)
-                    if x is not y3 and not any(x is f for k, f in feats.items() if k != "res2"):
+                    if x is not y3 and not any(x is f for k, f in feats.items() if k in FPN_IN_FEATURES):
                         pool.put(x)
                     x = y3
                     continue
@@ -843,7 +875,7 @@ class DensePlan:
                     pool.put(y1)
                     if b == 0 and sc is not None and sc is not y3:
                         pool.put(sc)
-                    if x is not y3 and not any(x is f for k, f in feats.items() if k != "res2"):
+                    if x is not y3 and not any(x is f for k, f in feats.items() if k in FPN_IN_FEATURES):
                         pool.put(x)
                     x = y3
                     continue
@@ -914,7 +946,7 @@ class DensePlan:
                 pool.put(y2)
                 if b == 0 and sc is not None:
                     pool.put(sc)
-                if not any(x is f for k, f in feats.items() if k != "res2"):
+                if not any(x is f for k, f in feats.items() if k in FPN_IN_FEATURES):
                     pool.put(x)          # res3/res4 outputs stay alive for the FPN laterals
                 x = y3
             feats["res%d" % (si + 2)] = x
@@ -928,10 +960,18 @@ class DensePlan:
             outs["p%d" % lvl] = conv("fpn_output%d" % lvl, lat, 3, 1, 1, 0)
             prev = lat
         p6 = conv("p6", outs["p5"], 3, 2, 1, 0)
-        p6r = pool.get(n, p6.h, p6.w, p6.c)
-        self.calls.append(FnCall(L.dafne_relu_copy_bf16_hip, (_lib.ptr(p6.t), _lib.ptr(p6r.t), p6.t.numel()),
-                                 (p6, p6r), "relu_copy"))
-        p7 = conv("p7", p6r, 3, 2, 1, 0)
+        # P7 = conv(relu(P6)), P6 itself stays un-rectified as a head input: conv_wr rectifies its pixel operand on load
+        # (F_RELU_INPUT); DAFNE_P7_RELU_IN=0, or a P7 that conv_wr does not take: a rectified copy of P6 (relu_copy)
+        w7, b7 = P["p7"]
+        ho7, wo7 = conv_out_hw(p6.h, p6.w, 3, 2, 1)
+        if (os.environ.get("DAFNE_P7_RELU_IN", "1") != "0" and wr_on and b7 is not None
+                and wr_takes(3, 2, p6.c, w7.shape[0], WR_NOMINAL_BATCH * ho7 * wo7)):
+            p7 = conv("p7", p6, 3, 2, 1, F_RELU_INPUT)
+        else:
+            p6r = pool.get(n, p6.h, p6.w, p6.c)
+            self.calls.append(FnCall(L.dafne_relu_copy_bf16_hip, (_lib.ptr(p6.t), _lib.ptr(p6r.t), p6.t.numel()),
+                                     (p6, p6r), "relu_copy"))
+            p7 = conv("p7", p6r, 3, 2, 1, 0)
         outs["p6"], outs["p7"] = p6, p7
         self.features = [outs[k] for k in ("p3", "p4", "p5", "p6", "p7")]
         self.head_start = len(self.calls)          # launches [0, head_start) are backbone + FPN, the rest the head

@@ -219,6 +219,9 @@ int dafne_gather_detections_hip(const float* d_corners, const float* d_scores, c
 #define DAFNE_CONV_FRAG16 256u     /* dafne_conv3x3_c256_hip / _pair_hip only: d_wfrag is in the 16x16x32 fragment order (below) and the
                                     * launch runs on v_mfma_f32_16x16x32_bf16 (cheaper per flop on this package); fp32 sums in another
                                     * order than the 32x32x16 form: <= 1 bf16 ulp apart on an output, run-to-run identical */
+#define DAFNE_CONV_RELU_INPUT 512u  /* dafne_conv2d_wr_hip only: ReLU of the INPUT applied on load (per bf16: a set sign bit gives 0, anything
+                                    * else is unchanged -- dafne_relu_copy_bf16_hip's definition); bit-identical to that launch
+                                    * followed by the plain call */
 
 typedef struct dafne_conv_seg {
     const void* d_in;   /* bf16 [N, Hin+2, Win+2, Cin]; stem: [N, Hin, Win, 4] pre-padded */
@@ -295,7 +298,7 @@ int dafne_conv3x3_c256_hip(const dafne_conv_params* prm, const dafne_conv_seg* s
  * registers, pixel operand staged by DMA, and a DETERMINISTIC split-K: dafne_conv2d_wr_splits() workgroups share a tile,
  * each writes its fp32 partial (128 KB) to d_workspace, the last arriver sums them in slice order and runs the epilogue.
  * Same parameter block and result definition as dafne_conv2d_nhwc_bf16_hip for one segment with flags RELU / RESIDUAL /
- * UPSAMPLE_ADD (EXCLUSIVE is accepted and ignored: the slice count depends on the shape and the CU count only); 1x1 pad 0 or 3x3 pad 1, stride 1 / 2,
+ * UPSAMPLE_ADD / RELU_INPUT (EXCLUSIVE is accepted and ignored: the slice count depends on the shape and the CU count only); 1x1 pad 0 or 3x3 pad 1, stride 1 / 2,
  * Cin % 64 == 0, Cout % 256 == 0, bias required; else DAFNE_E_UNSUPPORTED (dafne_conv2d_wr_ok: 1 / 0).  One slice: K order
  * and epilogue expressions are dafne_conv2d_nhwc_bf16_hip's -> bit-identical output.  Several slices: the fp32 sum is
  * grouped by slices (fp32 rounding apart from the unsplit sum; run-to-run identical).  prm->d_weight is ignored;
@@ -467,6 +470,21 @@ size_t dafne_bottleneck_block_narrow_scratch_bytes(void);
 int dafne_bottleneck_block_narrow_hip(const void* d_in, const void* d_res, const void* d_wfrag, const float* d_bias2,
                                       const float* d_bias3, const float* d_bias_sc, const float* d_bias1, int n_images, int H, int W,
                                       void* d_out, void* d_next, void* d_scratch, size_t scratch_bytes, void* stream);
+/*
+ * The LAST res2 bottleneck body at the pixels res3 reads (same reference block with STRIDE_IN_1X1: res3.0.conv1 and
+ * res3.0.shortcut are 1x1 stride 2 pad 0; conv_blk_narrow_s2.hip).  With Ho = (H+1)/2, Wo = (W+1)/2, for i < Ho, j < Wo:
+ *   T(i,j) = relu(conv2(d_in)(2i,2j) + bias2)   (3x3, 64 -> 64, pad 1, evaluated at the even pixels = stride 2),
+ *   d_out(i,j) = relu(conv3(T)(i,j) + bias3 + d_res(2i,2j))   (1x1, 64 -> 256, identity shortcut).
+ * d_in [N,H+2,W+2,64], d_res [N,H+2,W+2,256], d_out the COMPACT map [N,Ho+2,Wo+2,256] (interior written, halo untouched).
+ * d_wfrag: dafne_bottleneck_block_narrow_hip's (engine.pack_blk_narrow(w2, w3)); only the conv2 and conv3 sections are read.
+ * 2 x 32 output-pixel tiles, any H, W: rows of out-of-image tile pixels are written to d_scratch
+ * (>= dafne_bottleneck_block_narrow_s2_scratch_bytes(); holds nothing afterwards).  d_out(i,j) is bit-identical to pixel
+ * (2i,2j) of dafne_bottleneck_block_narrow_hip's d_out (d_bias_sc == NULL, d_next == NULL).
+ */
+size_t dafne_bottleneck_block_narrow_s2_scratch_bytes(void);
+int dafne_bottleneck_block_narrow_s2_hip(const void* d_in, const void* d_res, const void* d_wfrag, const float* d_bias2,
+                                         const float* d_bias3, int n_images, int H, int W, void* d_out, void* d_scratch,
+                                         size_t scratch_bytes, void* stream);
 /*
  * A WHOLE res3 bottleneck body, optionally with the head of the next block, in one kernel (same reference block;
  * conv_blk_mid.hip):  T = relu(conv2(d_in) + bias2)  (3x3, 128 -> 128, pad 1; d_in = the block's conv1 output),
