@@ -22,15 +22,23 @@ def q8(x, qscale=1.0):
     return (x * qscale).clamp(-448.0, 448.0).to(F8).float()
 
 
-def run_fp8(xs, w, b, in_qscale, flags=0, gn_in=None, gn_stats=False, kernel=None):
+def run_fp8(xs, w, b, in_qscale, flags=0, gn_in=None, gn_stats=False, kernel=None,
+            gn_fin=None, guard_rows=None, launches=1, after_launch=None):
     """xs: list of [N,C,H,W] float maps (levels sharing the weights).  Returns (outputs NCHW float on the CPU, partial, call).
-    kernel: the kernel the call must land on (conv3x3_patch_fp8, the only fp8 kernel since round 6)."""
+    kernel: the kernel the call must land on (conv3x3_patch_fp8, the only fp8 kernel since round 6).
+    gn_fin: (stats, counters, eps) -> flag F_GNFIN (the last tile of every image finalises the statistics of the output).
+    guard_rows: the strict form of tests/test_gpu_groupnorm.py -- the partial buffer has num_tiles() + guard_rows rows and starts as
+    NaN, like the interior of the outputs.  launches: how often the call runs into the same buffers; after_launch(call) runs
+    after each of them (synchronised)."""
     from dafne_amd import engine, _lib
     d = dev()
     n, cin = xs[0].shape[:2]
     cout = w.shape[0]
     ins = [engine.Act.from_nchw(x.to(d)) for x in xs]
     outs = [engine.Act(n, x.shape[2], x.shape[3], cout, d) for x in xs]
+    if guard_rows is not None:
+        for o in outs:
+            o.t[:, 1:-1, 1:-1, :] = float("nan")
     wq, wscale = engine.pack_conv_fp8(w, d)
     bias = b.float().to(d).contiguous()
     segs = [(i.t, o.t, None, i.h, i.w, i.h, i.w) for i, o in zip(ins, outs)]
@@ -40,12 +48,19 @@ def run_fp8(xs, w, b, in_qscale, flags=0, gn_in=None, gn_stats=False, kernel=Non
     probe = engine.ConvCall(wq, bias, cin, cout, 3, 1, 1, flags, segs, n, gn_in=gn_in, fp8=(oscale, in_qscale))
     partial = None
     if gn_stats:
-        partial = torch.zeros(4096, cout // 8, 2, dtype=torch.float32, device=d)
-        probe = engine.ConvCall(wq, bias, cin, cout, 3, 1, 1, flags | engine.F_GN, segs, n, gn_partial=partial,
-                                gn_in=gn_in, fp8=(oscale, in_qscale))
+        if guard_rows is None:
+            partial = torch.zeros(4096, cout // 8, 2, dtype=torch.float32, device=d)
+        else:
+            partial = torch.full((probe.num_tiles() + guard_rows, cout // 8, 2), float("nan"), dtype=torch.float32, device=d)
+        flags |= engine.F_GN | (engine.F_GNFIN if gn_fin is not None else 0)
+        probe = engine.ConvCall(wq, bias, cin, cout, 3, 1, 1, flags, segs, n,
+                                gn_partial=partial, gn_in=gn_in, fp8=(oscale, in_qscale), gn_fin=gn_fin)
     assert probe.kernel_name() == (kernel or "conv3x3_patch_fp8")
-    probe(_lib.current_stream())
-    torch.cuda.synchronize()
+    for _ in range(launches):
+        probe(_lib.current_stream())
+        torch.cuda.synchronize()
+        if after_launch is not None:
+            after_launch(probe)
     for o in outs:      # the halo must still be zero
         assert float(o.t[:, 0].abs().max()) == 0 and float(o.t[:, -1].abs().max()) == 0
         assert float(o.t[:, :, 0].abs().max()) == 0 and float(o.t[:, :, -1].abs().max()) == 0
