@@ -87,6 +87,9 @@ SIGNATURES = {
     "dafne_poly_nms_f64_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dafne_poly_nms_f64_batched_hip": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_int, c_void_p,
                                                c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "dafne_hbb_nms_f64_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dafne_hbb_nms_f64_batched_hip": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p]),
     "dafne_select_over_all_levels_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                                  c_double, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                                  c_int, c_void_p]),
@@ -155,11 +158,14 @@ SIGNATURES = {
     "dafne_scene_merge_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dafne_scene_merge_rows_hip": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_uint64, c_int,
                                            c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dafne_scene_merge_hbb_rows_hip": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_uint64, c_int,
+                                               c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dafne_scene_views_workspace_bytes": (c_size_t, [ctypes.POINTER(ViewSrc), c_int, c_int, c_int]),
     "dafne_scene_views_u8_hip": (c_int, [ctypes.POINTER(ViewSrc), c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dafne_tta_candidates_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dafne_tta_candidates_hip": (c_int, [ctypes.POINTER(TtaView), c_int, c_int, c_int, c_int] + [c_void_p] * 10 + [c_size_t, c_void_p]),
     "dafne_scene_match_hip": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dafne_scene_match_hbb_hip": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dafne_scene_mark_workspace_bytes": (c_size_t, [c_int]),
     "dafne_scene_mark_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_double,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

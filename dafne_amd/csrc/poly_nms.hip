@@ -1886,6 +1886,167 @@ int dafne_select_over_all_levels_hip(const float* d_boxes8, const float* d_score
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------ horizontal-box NMS (DOTA Task2)
+// ResultMerge_multi_process.py:124-155 (py_cpu_nms, the NMS of mergebyrec :238-248) on fp64 rows [x1, y1, x2, y2, score]:
+// greedy, axis-aligned, +1 on widths, heights and areas, a later row survives a kept one iff ovr <= thresh.  The pair
+// predicate is a dozen fp64 operations, so a wave decides a whole 64 x 64 tile in registers (lane = row, the 64 columns from
+// LDS broadcasts) and writes the tile's mask words directly: no hull pre-filter, no pair lists.  Sort (rank by counting on the
+// fp64 scores, nms_prep_f64_kernel's rule), greedy reduce and compaction are the polygon NMS's stages on a workspace that
+// holds only what they read.  (-ffp-contract=off: every operation below rounds on its own, as numpy's does.)
+namespace {
+
+// np.maximum(0.0, t): a NaN stays a NaN
+__device__ __forceinline__ double max0(double t) { return t > 0.0 ? t : (t != t ? t : 0.0); }
+
+// w.dbox: [N][Mp][4] (x1, y1, x2, y2), w.area: the +1 area; everything the tile stages do not read stays null
+size_t carve_hbb(NmsWs& w, void* base, int N, int m_cap) {
+    w = NmsWs{};
+    int Mp = (m_cap + kTile - 1) / kTile * kTile;
+    if (Mp == 0) Mp = kTile;
+    const int nblk = Mp / kTile;
+    const size_t n = (size_t)N, ntiles = (size_t)nblk * (nblk + 1) / 2;
+    dafne::WsCarver c(base);
+    w.Mp = Mp;
+    w.nblk = nblk;
+    w.rowflag = c.take<u64>(n * nblk);
+    w.keptw = c.take<u64>(n * nblk);                  // rowflag .. keptw are zeroed per call (contiguous)
+    w.order = c.take<int>(n * Mp);
+    w.sscore = c.take<float>(n * Mp);
+    w.area = c.take<double>(n * Mp);
+    w.dbox = c.take<double>(n * Mp * 4);
+    w.mask_words = ntiles * kTile;
+    w.mask = c.take<u64>(n * w.mask_words);
+    return dafne::align_up(c.off, 256);
+}
+
+__global__ void __launch_bounds__(256) hbb_prep_f64_kernel(const double* __restrict__ dets5, const int* __restrict__ counts,
+                                                           int m_cap, NmsWs w) {
+    const int img = blockIdx.y;
+    const int M = img_count(counts, img, m_cap);
+    if ((int)(blockIdx.x * blockDim.x) >= M) return;
+    const double* d = dets5 + (size_t)img * m_cap * 5;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < M;
+    const double si = live ? d[(size_t)i * 5 + 4] : 0.0;
+    __shared__ double ss[256];
+    int rank = 0;
+    for (int j0 = 0; j0 < M; j0 += 256) {
+        const int j = j0 + threadIdx.x;
+        ss[threadIdx.x] = j < M ? d[(size_t)j * 5 + 4] : -INFINITY;
+        __syncthreads();
+#pragma unroll 8
+        for (int jj = 0; jj < 256; jj++) {
+            const double v = ss[jj];
+            rank += (v > si) || (v == si && j0 + jj > i);     // argsort(kind="stable")[::-1]
+        }
+        __syncthreads();
+    }
+    if (!live) return;
+    const size_t base = (size_t)img * w.Mp + rank;
+    const double x1 = d[(size_t)i * 5], y1 = d[(size_t)i * 5 + 1], x2 = d[(size_t)i * 5 + 2], y2 = d[(size_t)i * 5 + 3];
+    w.order[base] = i;
+    w.sscore[base] = (float)si;
+    w.dbox[base * 4] = x1;
+    w.dbox[base * 4 + 1] = y1;
+    w.dbox[base * 4 + 2] = x2;
+    w.dbox[base * 4 + 3] = y2;
+    w.area[base] = (x2 - x1 + 1.0) * (y2 - y1 + 1.0);
+}
+
+// One wave per tile of the upper triangle (four tiles per workgroup): lane r holds row rb * 64 + r, the tile's 64 columns
+// sit in LDS (five planes, read as broadcasts).  Bit c of lane r's word: row r suppresses column c.
+__global__ void __launch_bounds__(256) hbb_mask_kernel(const int* __restrict__ counts, int m_cap, double thresh, NmsWs w,
+                                                       long long ntiles) {
+    __shared__ double col_s[4][5][kTile];
+    const int img = blockIdx.y;
+    const int M = img_count(counts, img, m_cap);
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const long long t = (long long)blockIdx.x * 4 + wv;     // wave-uniform by construction
+    if (t >= ntiles) return;
+    int rb, cb;
+    tile_rc(t, w.nblk, rb, cb);
+    if (rb * kTile >= M || cb * kTile >= M) return;          // nms_class_reduce never reads a tile past the rows in use
+    const size_t ibase = (size_t)img * w.Mp;
+    const int grow = rb * kTile + lane, gcol = cb * kTile + lane;
+    double (&col)[5][kTile] = col_s[wv];
+    if (gcol < M) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) col[k][lane] = w.dbox[(ibase + gcol) * 4 + k];
+        col[4][lane] = w.area[ibase + gcol];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 5; k++) col[k][lane] = 0.0;
+    }
+    double x1 = 0.0, y1 = 0.0, x2 = 0.0, y2 = 0.0, ar = 0.0;
+    if (grow < M) {
+        x1 = w.dbox[(ibase + grow) * 4];
+        y1 = w.dbox[(ibase + grow) * 4 + 1];
+        x2 = w.dbox[(ibase + grow) * 4 + 2];
+        y2 = w.dbox[(ibase + grow) * 4 + 3];
+        ar = w.area[ibase + grow];
+    }
+    __builtin_amdgcn_wave_barrier();
+    const int clim = min(kTile, M - cb * kTile);
+    u64 word = 0ull;
+#pragma unroll 4
+    for (int c = 0; c < clim; c++) {
+        // py_cpu_nms:142-152, i = the kept (earlier) row, in that operation order
+        const double xx1 = fmax(x1, col[0][c]), yy1 = fmax(y1, col[1][c]);
+        const double xx2 = fmin(x2, col[2][c]), yy2 = fmin(y2, col[3][c]);
+        const double iw = max0(xx2 - xx1 + 1.0), ih = max0(yy2 - yy1 + 1.0);
+        const double inter = iw * ih;
+        const double ovr = inter / (ar + col[4][c] - inter);
+        if (!(ovr <= thresh)) word |= 1ull << c;             // a NaN suppresses: np.where(ovr <= thresh) leaves it out
+    }
+    if (rb == cb) word &= lane >= 63 ? 0ull : ~((2ull << lane) - 1ull);       // only later rows
+    if (grow >= M) word = 0ull;
+    w.mask[(size_t)img * w.mask_words + (size_t)t * kTile + lane] = word;
+    const u64 acts = __ballot(word != 0ull);
+    if (lane == 0 && acts) atomicOr(&w.rowflag[(size_t)img * w.nblk + rb], acts);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dafne_hbb_nms_f64_workspace_bytes(int n_images, int m_cap) {
+    if (n_images <= 0 || m_cap < 0) return 0;
+    NmsWs w;
+    return carve_hbb(w, nullptr, n_images, m_cap);
+}
+
+int dafne_hbb_nms_f64_batched_hip(const double* d_dets5, const int32_t* d_counts, int n_images, int m_cap, double thresh,
+                                  int64_t* d_keep, int32_t* d_num_keep, void* d_ws, size_t ws_bytes, void* stream) {
+    if (n_images <= 0 || m_cap < 0 || !d_num_keep) return dafne::fail(DAFNE_E_INVALID, "hbb_nms_f64: bad args");
+    hipStream_t st = (hipStream_t)stream;
+    if (m_cap == 0) {
+        DAFNE_HIP_TRY(hipMemsetAsync(d_num_keep, 0, sizeof(int32_t) * n_images, st));
+        return DAFNE_OK;
+    }
+    if (!d_dets5 || !d_keep || !d_ws) return dafne::fail(DAFNE_E_INVALID, "hbb_nms_f64: null pointer");
+    NmsWs w;
+    const size_t need = carve_hbb(w, d_ws, n_images, m_cap);
+    if (ws_bytes < need) return dafne::fail(DAFNE_E_WORKSPACE, "hbb_nms_f64: workspace %zu < %zu", ws_bytes, need);
+    if (w.nblk > kMaxBlk) return dafne::fail(DAFNE_E_UNSUPPORTED, "hbb_nms_f64: m_cap %d > %d", m_cap, kMaxBlk * kTile);
+    const long long ntiles = (long long)w.nblk * (w.nblk + 1) / 2;
+    DAFNE_HIP_TRY(hipMemsetAsync(w.rowflag, 0, (size_t)((char*)(w.keptw + (size_t)n_images * w.nblk) - (char*)w.rowflag), st));
+    hipLaunchKernelGGL(hbb_prep_f64_kernel, dim3((m_cap + 255) / 256, n_images), dim3(256), 0, st, d_dets5, d_counts, m_cap, w);
+    int rc = dafne::check_launch("hbb_prep");
+    if (rc) return rc;
+    hipLaunchKernelGGL(hbb_mask_kernel, dim3((unsigned)((ntiles + 3) / 4), n_images), dim3(256), 0, st, d_counts, m_cap, thresh, w,
+                       ntiles);
+    if ((rc = dafne::check_launch("hbb_mask"))) return rc;
+    DAFNE_MAX_LDS_ONCE(kFastBlk * 65 * (int)sizeof(u64), (const void*)nms_class_reduce_kernel);
+    hipLaunchKernelGGL(nms_class_reduce_kernel, dim3(1, n_images), dim3(kReduceThreads), (size_t)kFastBlk * 65 * sizeof(u64), st,
+                       d_counts, m_cap, w);
+    if ((rc = dafne::check_launch("nms_class_reduce"))) return rc;
+    hipLaunchKernelGGL(nms_compact_kernel, dim3(n_images), dim3(kReduceThreads), 0, st, d_counts, m_cap, 0, w,
+                       reinterpret_cast<long long*>(d_keep), d_num_keep);
+    return dafne::check_launch("nms_compact");
+}
+
+}  // extern "C"
+
 // ----------------------------------------------------------------------------------------------- whole-scene merge rows
 // The tile merge after the Task1 text round trip (dota_evaluation._generate_task_1_files writes "%s %.4f %.2f .. %.2f",
 // ResultMerge_multi_process.mergebypoly parses the lines back and shifts them into the scene with poly2origpoly) as the fp64
@@ -1944,7 +2105,10 @@ __device__ __forceinline__ double quantise(float v, double scale) {
     return rint((double)v * scale) / scale;
 }
 
-// one block per tile: stable per-class rank of every row (wave ballots, waves in order, chunks in order), then the row
+// one block per tile: stable per-class rank of every row (wave ballots, waves in order, chunks in order), then the row.
+// ROW 9: the Task1 row (8 coordinates + score).  ROW 5: its horizontal box (dota_utils.py:122-127 dots4ToRec4 of the same
+// quantised, shifted coordinates: xmin, ymin, xmax, ymax) + the same score -- the Task2 row of mergebyrec.
+template <int ROW>
 __global__ void __launch_bounds__(kMergeThreads) merge_write_kernel(const float* __restrict__ rows, const int32_t* __restrict__ counts,
                                                                     int k_cap, const int32_t* __restrict__ tile_info, int n_scenes,
                                                                     int n_classes,
@@ -1982,15 +2146,25 @@ __global__ void __launch_bounds__(kMergeThreads) merge_write_kernel(const float*
             for (int w = 0; w < wave; w++) pos += wcnt[w][c];
             if (pos < m_cap) {
                 const size_t o = (size_t)s * n_classes + c;
-                double* d = dets + (o * m_cap + pos) * 9;
+                double* d = dets + (o * m_cap + pos) * ROW;
+                double q[8];
 #pragma unroll
-                for (int k = 0; k < 8; k++) d[k] = (quantise(row[k], 100.0) + (double)((k & 1) ? up : left)) / 1.0;
+                for (int k = 0; k < 8; k++) q[k] = (quantise(row[k], 100.0) + (double)((k & 1) ? up : left)) / 1.0;
+                if (ROW == 9) {
+#pragma unroll
+                    for (int k = 0; k < 8; k++) d[k] = q[k];
+                } else {
+                    d[0] = fmin(q[0], fmin(q[2], fmin(q[4], q[6])));
+                    d[1] = fmin(q[1], fmin(q[3], fmin(q[5], q[7])));
+                    d[2] = fmax(q[0], fmax(q[2], fmax(q[4], q[6])));
+                    d[3] = fmax(q[1], fmax(q[3], fmax(q[5], q[7])));
+                }
                 float v = row[8];
                 if (score_mode) {
                     const float sq = v * v;
                     v = sq / row[9];
                 }
-                d[8] = quantise(v, 10000.0);
+                d[ROW - 1] = quantise(v, 10000.0);
                 src[o * m_cap + pos] = t * k_cap + r;
             }
         }
@@ -2013,20 +2187,21 @@ size_t dafne_scene_merge_workspace_bytes(int n_tiles, int n_classes) {
     return 2 * dafne::align_up(sizeof(int32_t) * (size_t)n_tiles * n_classes, 256);
 }
 
-int dafne_scene_merge_rows_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap, const int32_t* d_tile_info,
-                               int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap, double* d_dets,
-                               int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
+// both merges: row_w 9 = the Task1 rows, 5 = the Task2 rows (same hist, scan and workspace)
+static int scene_merge_rows(const char* what, int row_w, const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap,
+                            const int32_t* d_tile_info, int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap,
+                            double* d_dets, int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
     if (!d_rows || !d_counts || !d_tile_info || !d_bucket_counts || !d_ws || n_tiles < 1 || k_cap < 1 || n_scenes < 1 ||
         m_cap < 0 || (score_mode != 0 && score_mode != 1))
-        return dafne::fail(DAFNE_E_INVALID, "scene_merge_rows: bad args (n_tiles %d, k_cap %d, n_scenes %d, m_cap %d, score_mode %d)",
+        return dafne::fail(DAFNE_E_INVALID, "%s: bad args (n_tiles %d, k_cap %d, n_scenes %d, m_cap %d, score_mode %d)", what,
                            n_tiles, k_cap, n_scenes, m_cap, score_mode);
     if (n_classes < 1 || n_classes > kMaxClasses)
-        return dafne::fail(DAFNE_E_INVALID, "scene_merge_rows: n_classes %d not in [1, %d]", n_classes, kMaxClasses);
-    if (m_cap > 0 && (!d_dets || !d_src)) return dafne::fail(DAFNE_E_INVALID, "scene_merge_rows: m_cap %d without d_dets / d_src", m_cap);
+        return dafne::fail(DAFNE_E_INVALID, "%s: n_classes %d not in [1, %d]", what, n_classes, kMaxClasses);
+    if (m_cap > 0 && (!d_dets || !d_src)) return dafne::fail(DAFNE_E_INVALID, "%s: m_cap %d without d_dets / d_src", what, m_cap);
     if ((size_t)n_tiles * k_cap > (size_t)INT32_MAX)
-        return dafne::fail(DAFNE_E_UNSUPPORTED, "scene_merge_rows: %d tiles x %d rows overflow the int32 back-index", n_tiles, k_cap);
+        return dafne::fail(DAFNE_E_UNSUPPORTED, "%s: %d tiles x %d rows overflow the int32 back-index", what, n_tiles, k_cap);
     if (ws_bytes < dafne_scene_merge_workspace_bytes(n_tiles, n_classes))
-        return dafne::fail(DAFNE_E_WORKSPACE, "scene_merge_rows: workspace %zu < %zu", ws_bytes,
+        return dafne::fail(DAFNE_E_WORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes,
                            dafne_scene_merge_workspace_bytes(n_tiles, n_classes));
     hipStream_t st = (hipStream_t)stream;
     dafne::WsCarver c(d_ws);
@@ -2041,9 +2216,27 @@ int dafne_scene_merge_rows_hip(const float* d_rows, const int32_t* d_counts, int
                        offs, d_bucket_counts);
     rc = dafne::check_launch("scene_merge_scan");
     if (rc || m_cap == 0) return rc;
-    hipLaunchKernelGGL(merge_write_kernel, dim3(n_tiles), dim3(kMergeThreads), 0, st, d_rows, d_counts, k_cap, d_tile_info,
-                       n_scenes, n_classes, (unsigned long long)skip_mask, score_mode, offs, m_cap, d_dets, d_src);
+    if (row_w == 9)
+        hipLaunchKernelGGL(merge_write_kernel<9>, dim3(n_tiles), dim3(kMergeThreads), 0, st, d_rows, d_counts, k_cap, d_tile_info,
+                           n_scenes, n_classes, (unsigned long long)skip_mask, score_mode, offs, m_cap, d_dets, d_src);
+    else
+        hipLaunchKernelGGL(merge_write_kernel<5>, dim3(n_tiles), dim3(kMergeThreads), 0, st, d_rows, d_counts, k_cap, d_tile_info,
+                           n_scenes, n_classes, (unsigned long long)skip_mask, score_mode, offs, m_cap, d_dets, d_src);
     return dafne::check_launch("scene_merge_write");
+}
+
+int dafne_scene_merge_rows_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap, const int32_t* d_tile_info,
+                               int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap, double* d_dets,
+                               int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
+    return scene_merge_rows("scene_merge_rows", 9, d_rows, d_counts, n_tiles, k_cap, d_tile_info, n_scenes, n_classes, skip_mask,
+                            score_mode, m_cap, d_dets, d_bucket_counts, d_src, d_ws, ws_bytes, stream);
+}
+
+int dafne_scene_merge_hbb_rows_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap, const int32_t* d_tile_info,
+                                   int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap, double* d_dets5,
+                                   int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
+    return scene_merge_rows("scene_merge_hbb_rows", 5, d_rows, d_counts, n_tiles, k_cap, d_tile_info, n_scenes, n_classes,
+                            skip_mask, score_mode, m_cap, d_dets5, d_bucket_counts, d_src, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"
@@ -2133,6 +2326,53 @@ __global__ void __launch_bounds__(64) scene_match_kernel(const double* __restric
     }
 }
 
+// Task2 (horizontal boxes): detections and ground truth are [x0, y0, x1, y1] rectangles and `ov` IS voc_eval.py:158-173's
+// inters / uni (+1 on widths, heights and both areas, that operation order) -- the DOTA devkit's Task2 evaluation is voc_eval
+// stopped after its hull stage.  One wave per detection, lanes stride the bucket; a lane keeps its first maximum (strict `>`
+// in ascending index), the wave then keeps the largest value and, among equal values, the lowest index (np.argmax).
+__global__ void __launch_bounds__(64) scene_match_hbb_kernel(const double* __restrict__ dets, const int32_t* __restrict__ bucket,
+                                                             const double* __restrict__ gt, const int32_t* __restrict__ gt_offs,
+                                                             int n_buckets, int n_gt, double* __restrict__ ovmax_out,
+                                                             int32_t* __restrict__ jmax_out) {
+    const int lane = threadIdx.x;
+    const size_t d = blockIdx.x;
+    const Hull hd{dets[d * 4], dets[d * 4 + 1], dets[d * 4 + 2], dets[d * 4 + 3]};
+    const int b = bucket[d];
+    int g0 = 0, g1 = 0;
+    if (b >= 0 && b < n_buckets) {
+        g0 = gt_offs[b];
+        g1 = gt_offs[b + 1];
+        g0 = g0 < 0 ? 0 : (g0 > n_gt ? n_gt : g0);
+        g1 = g1 < g0 ? g0 : (g1 > n_gt ? n_gt : g1);
+    }
+    double ovmax = -HUGE_VAL;
+    int jmax = -1;
+    for (int g = g0 + lane; g < g1; g += kTile) {
+        const Hull hg{gt[(size_t)g * 4], gt[(size_t)g * 4 + 1], gt[(size_t)g * 4 + 2], gt[(size_t)g * 4 + 3]};
+        const double iw = fmax(fmin(hg.x1, hd.x1) - fmax(hg.x0, hd.x0) + 1.0, 0.0);
+        const double ih = fmax(fmin(hg.y1, hd.y1) - fmax(hg.y0, hd.y0) + 1.0, 0.0);
+        const double inters = iw * ih;
+        const double uni = (hd.x1 - hd.x0 + 1.0) * (hd.y1 - hd.y0 + 1.0) + (hg.x1 - hg.x0 + 1.0) * (hg.y1 - hg.y0 + 1.0) - inters;
+        const double ov = inters / uni;
+        if (ov > ovmax) {
+            ovmax = ov;
+            jmax = g - g0;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double v = __shfl_xor(ovmax, o, 64);
+        const int j = __shfl_xor(jmax, o, 64);
+        if (j >= 0 && (jmax < 0 || v > ovmax || (v == ovmax && j < jmax))) {
+            ovmax = v;
+            jmax = j;
+        }
+    }
+    if (lane == 0) {
+        ovmax_out[d] = ovmax;
+        jmax_out[d] = jmax;
+    }
+}
+
 __device__ __forceinline__ int match_gt_index(const int32_t* bucket, const int32_t* gt_offs, int n_buckets, int n_gt, int d, int j) {
     const int b = bucket[d];
     if (j < 0 || b < 0 || b >= n_buckets) return -1;
@@ -2189,6 +2429,17 @@ int dafne_scene_match_hip(const double* d_dets, const int32_t* d_bucket, int n, 
     hipLaunchKernelGGL(scene_match_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, d_dets, d_bucket, d_gt, d_gt_offsets,
                        d_gt_offsets ? n_buckets : 0, n_gt, d_ovmax, d_jmax);
     return dafne::check_launch("scene_match");
+}
+
+int dafne_scene_match_hbb_hip(const double* d_dets, const int32_t* d_bucket, int n, const double* d_gt, const int32_t* d_gt_offsets,
+                              int n_buckets, int n_gt, double* d_ovmax, int32_t* d_jmax, void* stream) {
+    if (n < 0 || n_gt < 0 || n_buckets < 0) return dafne::fail(DAFNE_E_INVALID, "scene_match_hbb: bad sizes (n %d, n_gt %d, n_buckets %d)", n, n_gt, n_buckets);
+    if (n == 0) return DAFNE_OK;
+    if (!d_dets || !d_bucket || !d_ovmax || !d_jmax || (n_buckets > 0 && !d_gt_offsets) || (n_gt > 0 && !d_gt))
+        return dafne::fail(DAFNE_E_INVALID, "scene_match_hbb: null pointer");
+    hipLaunchKernelGGL(scene_match_hbb_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, d_dets, d_bucket, d_gt, d_gt_offsets,
+                       d_gt_offsets ? n_buckets : 0, n_gt, d_ovmax, d_jmax);
+    return dafne::check_launch("scene_match_hbb");
 }
 
 size_t dafne_scene_mark_workspace_bytes(int n_gt) {

@@ -12,10 +12,15 @@ Here every original image of a file is one row of ONE batched launch of the rota
 the hot path (`dafne_poly_nms_f64_batched_hip`: fp64 rows, the reference's hull pre-test as part of
 the predicate), so the keep lists are the reference's.
 
-Same entry points and argument meaning: mergebypoly(src, dst), mergebase(src, dst, nms),
+Same entry points and argument meaning: mergebypoly(src, dst), mergebyrec(src, dst), mergebase(src, dst, nms),
 mergesingle(dst, nms, fullname), nmsbynamedict(nameboxdict, nms, thresh), poly2origpoly(...).
 `nms` is a callable (float64 [M,9], thresh) -> kept indices; the default is the device one.
 There is no CPU fallback: without libdafne_amd.so / a GPU the calls raise.
+
+DOTA Task2 (horizontal boxes, `imgname score xmin ymin xmax ymax`): mergebyrec (:238-248) is mergebase with py_cpu_nms
+(:124-155), the greedy axis-aligned NMS with the +1 pixel convention, here dafne_hbb_nms_f64_batched_hip on [M,5] rows.
+The reference never writes the tile-level Task2 text mergebyrec reads; task1_to_task2 makes it from the Task1 files with
+dota_utils.dots4ToRec4 (dafne/utils/dota_utils.py:122-127).
 """
 import os
 import re
@@ -33,8 +38,11 @@ _RATE = re.compile(r"__([\d+\.]+)__\d+___")
 _INT = re.compile(r"\d+")
 
 
-def _merge_nms_batched(arrays, thresh, strict_hbb=True, device=None):
-    """arrays: list of float64 [M_i, 9].  One device launch per size bucket; returns list of keep lists."""
+def _merge_nms_batched(arrays, thresh, strict_hbb=True, device=None, width=9):
+    """arrays: list of float64 [M_i, width].  One device launch per size bucket; returns list of keep lists.
+    width 9: polygon rows (dafne_poly_nms_f64_batched_hip); width 5: horizontal boxes (dafne_hbb_nms_f64_batched_hip)."""
+    if width not in (5, 9):
+        raise ValueError("_merge_nms_batched: rows of %r values (9: polygon + score, 5: horizontal box + score)" % (width,))
     L = _lib.load()
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
     out = [None] * len(arrays)
@@ -54,24 +62,33 @@ def _merge_nms_batched(arrays, thresh, strict_hbb=True, device=None):
                 n += 1
             ids = todo[pos:pos + n]
             pos += n
-            host = np.zeros((n, m_cap, 9), dtype=np.float64)
+            host = np.zeros((n, m_cap, width), dtype=np.float64)
             counts = np.zeros(n, dtype=np.int32)
             for k, i in enumerate(ids):
-                a = np.ascontiguousarray(arrays[i], dtype=np.float64).reshape(-1, 9)
+                a = np.ascontiguousarray(arrays[i], dtype=np.float64).reshape(-1, width)
                 host[k, :a.shape[0]] = a
                 counts[k] = a.shape[0]
             d = torch.from_numpy(host).to(dev)
             c = torch.from_numpy(counts).to(dev)
             keep = torch.empty((n, m_cap), dtype=torch.int64, device=dev)
             nk = torch.zeros(n, dtype=torch.int32, device=dev)
-            nbytes = L.dafne_poly_nms_f64_workspace_bytes(n, m_cap)
-            if nbytes == 0:
-                raise _lib.DafneHipError("poly_nms_f64: bad size %d x %d" % (n, m_cap))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.dafne_poly_nms_f64_batched_hip(_lib.ptr(d), _lib.ptr(c), n, m_cap, float(thresh),
-                                                        1 if strict_hbb else 0, _lib.ptr(keep), _lib.ptr(nk),
-                                                        _lib.ptr(ws), nbytes, 0, _lib.current_stream()),
-                       "dafne_poly_nms_f64_batched_hip")
+            if width == 5:
+                nbytes = L.dafne_hbb_nms_f64_workspace_bytes(n, m_cap)
+                if nbytes == 0:
+                    raise _lib.DafneHipError("hbb_nms_f64: bad size %d x %d" % (n, m_cap))
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                _lib.check(L.dafne_hbb_nms_f64_batched_hip(_lib.ptr(d), _lib.ptr(c), n, m_cap, float(thresh), _lib.ptr(keep),
+                                                           _lib.ptr(nk), _lib.ptr(ws), nbytes, _lib.current_stream()),
+                           "dafne_hbb_nms_f64_batched_hip")
+            else:
+                nbytes = L.dafne_poly_nms_f64_workspace_bytes(n, m_cap)
+                if nbytes == 0:
+                    raise _lib.DafneHipError("poly_nms_f64: bad size %d x %d" % (n, m_cap))
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                _lib.check(L.dafne_poly_nms_f64_batched_hip(_lib.ptr(d), _lib.ptr(c), n, m_cap, float(thresh),
+                                                            1 if strict_hbb else 0, _lib.ptr(keep), _lib.ptr(nk),
+                                                            _lib.ptr(ws), nbytes, 0, _lib.current_stream()),
+                           "dafne_poly_nms_f64_batched_hip")
             kh, nh = keep.cpu().numpy(), nk.cpu().numpy()
             for k, i in enumerate(ids):
                 out[i] = kh[k, :nh[k]].tolist()
@@ -86,6 +103,11 @@ def py_cpu_nms_poly_fast(dets, thresh):
 def py_cpu_nms_poly(dets, thresh):
     """Reference :24-58 (no hull pre-test), on the GPU."""
     return _merge_nms_batched([np.asarray(dets, dtype=np.float64).reshape(-1, 9)], thresh, False)[0]
+
+
+def py_cpu_nms(dets, thresh):
+    """Name kept from the reference (:124-155); runs on the GPU.  dets: [M,5] float64 (x1, y1, x2, y2, score)."""
+    return _merge_nms_batched([np.asarray(dets, dtype=np.float64).reshape(-1, 5)], thresh, width=5)[0]
 
 
 def poly2origpoly(poly, x, y, rate):
@@ -121,6 +143,8 @@ def nmsbynamedict(nameboxdict, nms, thresh):
     if nms in (py_cpu_nms_poly_fast, py_cpu_nms_poly):
         keeps = _merge_nms_batched([np.array(nameboxdict[n], dtype=np.float64) for n in names], thresh,
                                    nms is py_cpu_nms_poly_fast)
+    elif nms is py_cpu_nms:
+        keeps = _merge_nms_batched([np.array(nameboxdict[n], dtype=np.float64) for n in names], thresh, width=5)
     else:
         keeps = [nms(np.array(nameboxdict[n]), thresh) for n in names]
     return {n: [nameboxdict[n][i] for i in k] for n, k in zip(names, keeps)}
@@ -158,3 +182,33 @@ def mergebase_parallel(srcpath, dstpath, nms):
 def mergebypoly(srcpath, dstpath):
     """srcpath: Task1 files on tiles; dstpath: merged files on original images (:229-243)."""
     mergebase_parallel(srcpath, dstpath, py_cpu_nms_poly_fast)
+
+
+def mergebyrec(srcpath, dstpath):
+    """srcpath: Task2 files on tiles (`name score xmin ymin xmax ymax`); dstpath: merged files on original images (:238-248)."""
+    mergebase(srcpath, dstpath, py_cpu_nms)
+
+
+def dots4ToRec4(poly):
+    """dota_utils.py:122-127: poly = four (x, y) pairs -> xmin, ymin, xmax, ymax."""
+    xs, ys = [p[0] for p in poly], [p[1] for p in poly]
+    return min(xs), min(ys), max(xs), max(ys)
+
+
+def task1_to_task2(src_dir, dst_dir):
+    """Every Task1_<class>.txt of src_dir -> Task2_<class>.txt in dst_dir: the name and score tokens verbatim, the
+    coordinates dots4ToRec4 of the parsed floats written "%.2f" -- the tile-level Task2 text mergebyrec reads."""
+    os.makedirs(dst_dir, exist_ok=True)
+    for fn in sorted(os.listdir(src_dir)):
+        if not (fn.startswith("Task1_") and fn.endswith(".txt")):
+            continue
+        with open(os.path.join(src_dir, fn), "r") as f:
+            lines = f.readlines()
+        with open(os.path.join(dst_dir, "Task2_" + fn[len("Task1_"):]), "w") as f:
+            for raw in lines:
+                tok = raw.strip().split(" ")
+                if len(tok) < 10:
+                    continue
+                v = [float(t) for t in tok[2:10]]
+                rec = dots4ToRec4([(v[0], v[1]), (v[2], v[3]), (v[4], v[5]), (v[6], v[7])])
+                f.write(tok[0] + " " + tok[1] + " " + " ".join("%.2f" % x for x in rec) + "\n")

@@ -64,14 +64,32 @@ def load_scene_labels(label_dir, scene_names, classnames, parse_gt=dota_evaluati
             "scene_names": list(scene_names), "classnames": classnames}
 
 
-def match_scenes(results, labels, n_classes, iou_thresh):
+def rec4(boxes):
+    """dota_utils.py:122-127 (dots4ToRec4) on [N,8] rows -> [N,4] xmin, ymin, xmax, ymax: the horizontal ground truth of
+    parse_dota_rec (:109-119)."""
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 8)
+    return np.stack([b[:, 0::2].min(1), b[:, 1::2].min(1), b[:, 0::2].max(1), b[:, 1::2].max(1)], axis=1) if b.shape[0] else \
+        np.zeros((0, 4), dtype=np.float64)
+
+
+def match_scenes(results, labels, n_classes, iou_thresh, task="task1"):
     """results: detect_scenes' dicts (corners [K,8] f64, scores [K] f64, labels [K], device tensors), one per scene of
     `labels`, in the same order.  Everything stays on the device; nothing is read back here.  -> dict of device tensors over
     the N detections in call order (scene by scene, each scene in keep order):
       "ovmax" f64, "jmax" int32 (index inside the (scene, class) bucket, -1: no candidate), "tp" / "fp" uint8,
       "rank" int64 (position in its class's stably sorted order), "label" int64 (n_classes: a label outside the classes, in no
       class's list), "scene" int64, "order" int64 (the detections class-major, each class in sorted order: order[k] indexes
-      the arrays above) and "class_start" [n_classes + 2] int64 (class c is order[class_start[c]:class_start[c + 1]])."""
+      the arrays above) and "class_start" [n_classes + 2] int64 (class c is order[class_start[c]:class_start[c + 1]]).
+    task "task2": the results' "task2" entries (boxes [K,4] f64) against rec4 of the labels' boxes, ov = voc_eval's own
+    inters / uni on the rectangles over every box of the bucket (dafne_scene_match_hbb_hip); everything else as above."""
+    if task not in ("task1", "task2"):
+        raise ValueError("match_scenes: task %r is neither \"task1\" nor \"task2\"" % (task,))
+    hbb = task == "task2"
+    if hbb:
+        if any("task2" not in r for r in results):
+            raise ValueError("match_scenes: task2 needs the results of detect_scenes(..., tasks=(\"task1\", \"task2\"))")
+        results = [{"corners": r["task2"]["boxes"], "scores": r["task2"]["scores"], "labels": r["task2"]["labels"]} for r in results]
+    wd = 4 if hbb else 8
     C = int(n_classes)
     S = len(results)
     off = labels["offsets"]
@@ -81,13 +99,13 @@ def match_scenes(results, labels, n_classes, iou_thresh):
     L = _lib.load()
     with torch.cuda.device(dev):
         if S:
-            corners = torch.cat([r["corners"].reshape(-1, 8) for r in results]).to(device=dev, dtype=torch.float64).contiguous()
+            corners = torch.cat([r["corners"].reshape(-1, wd) for r in results]).to(device=dev, dtype=torch.float64).contiguous()
             scores = torch.cat([r["scores"].reshape(-1) for r in results]).to(device=dev, dtype=torch.float64)
             lab = torch.cat([r["labels"].reshape(-1) for r in results]).to(device=dev, dtype=torch.int64)
             sizes = torch.tensor([int(r["scores"].numel()) for r in results], dtype=torch.int64)
             scene = torch.repeat_interleave(torch.arange(S, dtype=torch.int64), sizes).to(dev)
         else:
-            corners = torch.zeros((0, 8), dtype=torch.float64, device=dev)
+            corners = torch.zeros((0, wd), dtype=torch.float64, device=dev)
             scores = torch.zeros(0, dtype=torch.float64, device=dev)
             lab = scene = torch.zeros(0, dtype=torch.int64, device=dev)
         N = int(corners.shape[0])
@@ -106,7 +124,7 @@ def match_scenes(results, labels, n_classes, iou_thresh):
         rank32 = rank.to(torch.int32)
 
         G = int(labels["boxes"].shape[0])
-        gt = torch.from_numpy(np.ascontiguousarray(labels["boxes"], dtype=np.float64)).to(dev)
+        gt = torch.from_numpy(np.ascontiguousarray(rec4(labels["boxes"]) if hbb else labels["boxes"], dtype=np.float64)).to(dev)
         offs = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int32)).to(dev)
         diff = torch.from_numpy(np.ascontiguousarray(labels["difficult"]).astype(np.uint8)).to(dev)
         ovmax = torch.empty(N, dtype=torch.float64, device=dev)
@@ -114,8 +132,12 @@ def match_scenes(results, labels, n_classes, iou_thresh):
         tp = torch.empty(N, dtype=torch.uint8, device=dev)
         fp = torch.empty(N, dtype=torch.uint8, device=dev)
         st = _lib.current_stream()
-        _lib.check(L.dafne_scene_match_hip(_lib.ptr(corners), _lib.ptr(bucket), N, _lib.ptr(gt), _lib.ptr(offs), S * C, G,
-                                           _lib.ptr(ovmax), _lib.ptr(jmax), st), "dafne_scene_match_hip")
+        if hbb:
+            _lib.check(L.dafne_scene_match_hbb_hip(_lib.ptr(corners), _lib.ptr(bucket), N, _lib.ptr(gt), _lib.ptr(offs), S * C, G,
+                                                   _lib.ptr(ovmax), _lib.ptr(jmax), st), "dafne_scene_match_hbb_hip")
+        else:
+            _lib.check(L.dafne_scene_match_hip(_lib.ptr(corners), _lib.ptr(bucket), N, _lib.ptr(gt), _lib.ptr(offs), S * C, G,
+                                               _lib.ptr(ovmax), _lib.ptr(jmax), st), "dafne_scene_match_hip")
         nbytes = L.dafne_scene_mark_workspace_bytes(G)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         _lib.check(L.dafne_scene_mark_hip(_lib.ptr(rank32), _lib.ptr(ovmax), _lib.ptr(jmax), _lib.ptr(bucket), N, _lib.ptr(offs),
@@ -135,24 +157,27 @@ def curves_from_flags(tp, fp, npos):
     return rec, prec, voc_ap(rec, prec, True)
 
 
-def score_scenes(results, labels, classnames, cfg, output_folder=None):
+def score_scenes(results, labels, classnames, cfg, output_folder=None, task="task1"):
     """What task1.score_task1 returns for the same detections written with scene.write_task1_merged and the same label
     files -- {"task1": {<class>: ap, ..., "map": mean}}, the same floats -- without the files: match_scenes on the device,
     one host read of the flags, then rec / prec / ap per class with voc_ap (cumulative sums; no per-detection Python).
     Also returned: "rec" / "prec" ({class: array}, voc_eval's), "per_scene" [scenes, classes, 3] int64 = tp, fp, npos of every
     (scene, class), to find the scenes that cost the score, and "match" (match_scenes' device tensors).
     output_folder: results.txt as score_task1 writes it.  scores_overlap.csv is NOT written: it is the plotting input of the
-    reference and carries the reference's quirk of indexing the unsorted confidences."""
+    reference and carries the reference's quirk of indexing the unsorted confidences.
+    task="task2": DOTA's horizontal-box task on the results' "task2" entries -> {"task2": {...}}, results_task2.txt (never
+    results.txt).  The ground truth is dots4ToRec4 of the label boxes and the overlap is voc_eval's own hull stage
+    (voc_eval.py:158-173) -- the DOTA devkit's Task2 evaluation; the same sort, marking kernel and single host read."""
     classnames = list(classnames)
     C, S = len(classnames), len(results)
-    m = match_scenes(results, labels, C, cfg.TEST.IOU_TH)
+    m = match_scenes(results, labels, C, cfg.TEST.IOU_TH, task=task)
     order = m["order"]
     host = torch.stack([m["tp"][order].to(torch.int64), m["fp"][order].to(torch.int64), m["scene"][order]])
     host = torch.cat([host.reshape(-1), m["class_start"]]).cpu().numpy()          # the one host read
     N = int(order.shape[0])
     tp, fp, scene = host[:N], host[N:2 * N], host[2 * N:3 * N]
     start = host[3 * N:]
-    task = OrderedDict()
+    ap_table = OrderedDict()
     rec, prec = OrderedDict(), OrderedDict()
     per_scene = np.zeros((S, C, 3), dtype=np.int64)
     per_scene[:, :, 2] = labels["npos"]
@@ -163,11 +188,11 @@ def score_scenes(results, labels, classnames, cfg, output_folder=None):
         per_scene[:, c, 0] = np.bincount(scene[a:b], weights=tp[a:b], minlength=S)[:S]
         per_scene[:, c, 1] = np.bincount(scene[a:b], weights=fp[a:b], minlength=S)[:S]
         mean_ap += ap
-        task[name] = ap
-    task["map"] = mean_ap / len(classnames)
+        ap_table[name] = ap
+    ap_table["map"] = mean_ap / len(classnames)
     if output_folder is not None:
         os.makedirs(output_folder, exist_ok=True)
-        with open(os.path.join(output_folder, "results.txt"), "w") as f:
-            for k, v in task.items():
+        with open(os.path.join(output_folder, "results_task2.txt" if task == "task2" else "results.txt"), "w") as f:
+            for k, v in ap_table.items():
                 f.write(f"{k: <18}: {v:2.4f}\n")
-    return {"task1": task, "rec": rec, "prec": prec, "per_scene": per_scene, "match": m}
+    return {"task2" if task == "task2" else "task1": ap_table, "rec": rec, "prec": prec, "per_scene": per_scene, "match": m}

@@ -22,6 +22,12 @@ strict hull test).  write_task1_merged then writes what mergebypoly writes, byte
   tta_tile_rows(tta, scenes, ...)               every tile's merged TTA rows
   detect_scenes_tta(tta, scenes, ...)           OneStageRCNNWithTTA.detect_scenes
   write_task1_merged(results, names, classes, dst)
+  write_task2_merged(results, names, classes, dst)
+
+DOTA Task2 (horizontal boxes) is a second merge of the SAME tile rows: with tasks=("task1", "task2") the rows also become
+mergebyrec's f64 rows (dafne_scene_merge_hbb_rows_hip: dots4ToRec4 of the Task1 row) and go through py_cpu_nms on the device
+(dafne_hbb_nms_f64_batched_hip, thresh 0.1); every scene dict gains a "task2" entry and write_task2_merged writes what
+mergebyrec writes for the Task2 files task1_to_task2 makes of the tile-level Task1 files.  The detector runs once.
 
 Scene-level TTA runs the per-image TTA of every tile (modeling/tta.py: DotaDatasetMapperTTA's views, detect_packed without
 post-process, the inverse transforms, one rotated NMS + cap per tile) with views of many tiles batched: per TTA size one
@@ -134,11 +140,12 @@ def skip_mask(cfg):
     return (1 << 15) if bool(cfg.DATASETS.DOTA_REMOVE_CONTAINER_CRANE) else 0
 
 
-def merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, m_cap=None, overflow=None):
+def merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, m_cap=None, overflow=None, hbb=False):
     """rows [T,k_cap,18] f32 + counts [T] (device) + tile_info [T,3] int32 (left, up, scene) -> (dets [B,m_cap,9] f64,
     bucket counts [B] int32, src [B,m_cap] int32, m_cap) with B = n_scenes * n_classes.  m_cap None: sized from the bucket
     counts (a host read of B integers).  overflow: optional device int tensor, read in that same host read; nonzero
-    raises (rows the caller truncated)."""
+    raises (rows the caller truncated).  hbb: the Task2 rows instead, dets [B,m_cap,5] f64 (xmin, ymin, xmax, ymax, score);
+    buckets, counts and src are the same."""
     L = _lib.load()
     dev = rows.device
     T, k_cap = int(rows.shape[0]), int(rows.shape[1])
@@ -155,11 +162,13 @@ def merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         bcount = torch.empty(nb, dtype=torch.int32, device=dev)
 
+        fn, what = (L.dafne_scene_merge_hbb_rows_hip, "dafne_scene_merge_hbb_rows_hip") if hbb else \
+            (L.dafne_scene_merge_rows_hip, "dafne_scene_merge_rows_hip")
+
         def call(cap, dets, src):
-            _lib.check(L.dafne_scene_merge_rows_hip(_lib.ptr(rows), _lib.ptr(counts), T, k_cap, _lib.ptr(info), int(n_scenes),
-                                                    int(n_classes), int(skip), int(score_mode), int(cap), _lib.ptr(dets),
-                                                    _lib.ptr(bcount), _lib.ptr(src), _lib.ptr(ws), nbytes, _lib.current_stream()),
-                       "dafne_scene_merge_rows_hip")
+            _lib.check(fn(_lib.ptr(rows), _lib.ptr(counts), T, k_cap, _lib.ptr(info), int(n_scenes),
+                          int(n_classes), int(skip), int(score_mode), int(cap), _lib.ptr(dets),
+                          _lib.ptr(bcount), _lib.ptr(src), _lib.ptr(ws), nbytes, _lib.current_stream()), what)
         if m_cap is None:
             call(0, None, None)
             if overflow is None:
@@ -169,66 +178,101 @@ def merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_
                 if ovf:
                     raise _lib.DafneHipError("tile detections exceed the packed row capacity (%d): rows would be dropped" % k_cap)
                 m_cap = max(int(mx), 1)
-        dets = torch.empty((nb, m_cap, 9), dtype=torch.float64, device=dev)
+        dets = torch.empty((nb, m_cap, 5 if hbb else 9), dtype=torch.float64, device=dev)
         src = torch.empty((nb, m_cap), dtype=torch.int32, device=dev)
         call(m_cap, dets, src)
     return dets, bcount, src, m_cap
 
 
 def nms_buckets(dets, bcount, m_cap, thresh=NMS_THRESH):
-    """The tile merge's NMS (strict hull test) on every bucket, on the device: -> keep [B,m_cap] int64, num_keep [B]."""
+    """The tile merge's NMS on every bucket, on the device: -> keep [B,m_cap] int64, num_keep [B].  dets [B,m_cap,9]: the
+    polygon NMS with the strict hull test (mergebypoly); [B,m_cap,5]: the horizontal-box NMS (mergebyrec)."""
     L = _lib.load()
     dev = dets.device
     nb = int(dets.shape[0])
+    hbb = int(dets.shape[2]) == 5
+    ws_bytes = L.dafne_hbb_nms_f64_workspace_bytes if hbb else L.dafne_poly_nms_f64_workspace_bytes
+    what = "dafne_hbb_nms_f64_batched_hip" if hbb else "dafne_poly_nms_f64_batched_hip"
     keep = torch.empty((nb, m_cap), dtype=torch.int64, device=dev)
     nk = torch.zeros(nb, dtype=torch.int32, device=dev)
-    per = max(L.dafne_poly_nms_f64_workspace_bytes(1, m_cap), 1)
+    per = max(ws_bytes(1, m_cap), 1)
     step = max(1, min(nb, _NMS_WS_LIMIT // per))
     with torch.cuda.device(dev):
-        nbytes = L.dafne_poly_nms_f64_workspace_bytes(step, m_cap)
+        nbytes = ws_bytes(step, m_cap)
         if nbytes == 0:
-            raise _lib.DafneHipError("poly_nms_f64: bad size %d x %d" % (step, m_cap))
+            raise _lib.DafneHipError("%s: bad size %d x %d" % (what, step, m_cap))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         for b0 in range(0, nb, step):
             n = min(step, nb - b0)
-            _lib.check(L.dafne_poly_nms_f64_batched_hip(_lib.ptr(dets[b0:b0 + n]), _lib.ptr(bcount[b0:b0 + n]), n, m_cap,
-                                                        float(thresh), 1, _lib.ptr(keep[b0:b0 + n]), _lib.ptr(nk[b0:b0 + n]),
-                                                        _lib.ptr(ws), nbytes, 0, _lib.current_stream()),
-                       "dafne_poly_nms_f64_batched_hip")
+            if hbb:
+                rc = L.dafne_hbb_nms_f64_batched_hip(_lib.ptr(dets[b0:b0 + n]), _lib.ptr(bcount[b0:b0 + n]), n, m_cap, float(thresh),
+                                                     _lib.ptr(keep[b0:b0 + n]), _lib.ptr(nk[b0:b0 + n]), _lib.ptr(ws), nbytes,
+                                                     _lib.current_stream())
+            else:
+                rc = L.dafne_poly_nms_f64_batched_hip(_lib.ptr(dets[b0:b0 + n]), _lib.ptr(bcount[b0:b0 + n]), n, m_cap,
+                                                      float(thresh), 1, _lib.ptr(keep[b0:b0 + n]), _lib.ptr(nk[b0:b0 + n]),
+                                                      _lib.ptr(ws), nbytes, 0, _lib.current_stream())
+            _lib.check(rc, what)
     return keep, nk
 
 
-def merge_scenes(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, overflow=None):
-    """Tile rows -> per scene {"corners" [K,8] f64, "scores" [K] f64, "labels" [K] int64, "tile" [K], "row" [K]}: class by
-    class, each class in the NMS keep order (descending score) -- what mergebypoly writes for that scene.  overflow: see
-    merge_tile_rows."""
-    k_cap = int(rows.shape[1])
-    dets, bcount, src, m_cap = merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip, score_mode,
-                                               overflow=overflow)
+TASKS = ("task1", "task2")
+
+
+def _check_tasks(tasks):
+    tasks = tuple(tasks)
+    bad = [t for t in tasks if t not in TASKS]
+    if bad or "task1" not in tasks:
+        raise ValueError("tasks %r: a subset of %r that holds \"task1\" (the Task2 boxes are made of the Task1 rows)" % (tasks, TASKS))
+    return tasks
+
+
+def _kept_rows(dets, bcount, src, m_cap, n_scenes, n_classes, k_cap, box_key):
+    """NMS on every bucket + the kept rows per scene: class by class, each class in keep order."""
     keep, nk = nms_buckets(dets, bcount, m_cap)
     dev = dets.device
     nb = dets.shape[0]
+    wd = int(dets.shape[2])
     # the kept rows of every bucket, bucket-major (scene, then class): one host read, the kept counts
     valid = torch.arange(m_cap, device=dev)[None, :] < nk[:, None].to(torch.int64)
     flat = (torch.arange(nb, device=dev, dtype=torch.int64)[:, None] * m_cap + keep.clamp(0, m_cap - 1))[valid]
-    d = dets.reshape(-1, 9)[flat]
+    d = dets.reshape(-1, wd)[flat]
     s = src.reshape(-1)[flat].to(torch.int64)
     lab = (torch.arange(nb, device=dev, dtype=torch.int64)[:, None].expand(nb, m_cap) % n_classes)[valid]
     per_scene = nk.reshape(n_scenes, n_classes).sum(1).cpu().tolist()
     out = []
     o = 0
     for k in per_scene:
-        out.append({"corners": d[o:o + k, :8], "scores": d[o:o + k, 8], "labels": lab[o:o + k],
+        out.append({box_key: d[o:o + k, :wd - 1], "scores": d[o:o + k, wd - 1], "labels": lab[o:o + k],
                     "tile": s[o:o + k] // k_cap, "row": s[o:o + k] % k_cap})
         o += k
     return out
 
 
-def detect_scenes(model, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None):
+def merge_scenes(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, overflow=None, tasks=("task1",)):
+    """Tile rows -> per scene {"corners" [K,8] f64, "scores" [K] f64, "labels" [K] int64, "tile" [K], "row" [K]}: class by
+    class, each class in the NMS keep order (descending score) -- what mergebypoly writes for that scene.  overflow: see
+    merge_tile_rows.  With "task2" in tasks every dict also holds "task2": {"boxes" [K2,4] f64 (xmin, ymin, xmax, ymax),
+    "scores", "labels", "tile", "row"}, what mergebyrec writes for that scene, merged from the same tile rows."""
+    tasks = _check_tasks(tasks)
+    k_cap = int(rows.shape[1])
+    dets, bcount, src, m_cap = merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip, score_mode,
+                                               overflow=overflow)
+    out = _kept_rows(dets, bcount, src, m_cap, n_scenes, n_classes, k_cap, "corners")
+    if "task2" in tasks:
+        # the same buckets and counts: m_cap is known, no second read
+        dets5, bcount5, src5, _ = merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip, score_mode, m_cap=m_cap, hbb=True)
+        for r, r2 in zip(out, _kept_rows(dets5, bcount5, src5, m_cap, n_scenes, n_classes, k_cap, "boxes")):
+            r["task2"] = r2
+    return out
+
+
+def detect_scenes(model, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",)):
     """OneStageDetector.detect_scenes: device uint8 BGR scenes (HWC or CHW) -> one result per scene (merge_scenes' dicts,
-    plus "origins": the scene's tile origins in split order).  Tiles of all scenes go through detect_packed(pipelined=True)
+    plus "origins": the scene's tile origins in split order; tasks: see merge_scenes).  Tiles of all scenes go through detect_packed(pipelined=True)
     in batches of `batch` (the engine is batch-invariant: a tile's detections do not depend on its batch)."""
     from .data.loader import _to_chw_resized, inference_resize_shape
+    tasks = _check_tasks(tasks)
     if not scenes:
         return []
     cfg = model.cfg
@@ -261,7 +305,8 @@ def detect_scenes(model, scenes, patch_size=1024, overlap=200, batch=8, layout_h
         torch.cuda.current_stream().wait_stream(model.side_stream)
         rows = torch.cat([r for r, _ in parts])
         counts = torch.cat([c for _, c in parts])
-        res = merge_scenes(rows, counts, info, len(scenes), int(cfg.MODEL.DAFNE.NUM_CLASSES), skip_mask(cfg), task1_score_mode(cfg))
+        res = merge_scenes(rows, counts, info, len(scenes), int(cfg.MODEL.DAFNE.NUM_CLASSES), skip_mask(cfg), task1_score_mode(cfg),
+                           tasks=tasks)
     for r, org in zip(res, origins):
         r["origins"] = org
     return res
@@ -510,9 +555,10 @@ def tta_tile_rows(tta, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc
     return rows, counts, overflow, info, origins
 
 
-def detect_scenes_tta(tta, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None):
+def detect_scenes_tta(tta, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",)):
     """OneStageRCNNWithTTA.detect_scenes: device uint8 BGR scenes -> merge_scenes' dicts per scene (plus "origins"); "tile" /
     "row" index the tiles' merged TTA rows.  The host reads what merge_scenes reads (and the overflow flag with it)."""
+    tasks = _check_tasks(tasks)
     if not scenes:
         return []
     m = tta.model
@@ -520,7 +566,7 @@ def detect_scenes_tta(tta, scenes, patch_size=1024, overlap=200, batch=8, layout
     rows, counts, overflow, info, origins = tta_tile_rows(tta, scenes, patch_size, overlap, batch, layout_hwc)
     with torch.cuda.device(m.device):
         res = merge_scenes(rows, counts, info, len(scenes), int(cfg.MODEL.DAFNE.NUM_CLASSES), skip_mask(cfg),
-                           task1_score_mode(cfg), overflow=overflow)
+                           task1_score_mode(cfg), overflow=overflow, tasks=tasks)
     for r, org in zip(res, origins):
         r["origins"] = org
     return res
@@ -539,3 +585,22 @@ def write_task1_merged(results, scene_names, classnames, dst):
             for name, (corners, scores, labels) in zip(scene_names, host):
                 for i in np.nonzero(labels == c)[0]:
                     f.write(name + " " + str(float(scores[i])) + " " + " ".join(map(str, corners[i].tolist())) + "\n")
+
+
+def write_task2_merged(results, scene_names, classnames, dst):
+    """Task2_<class>.txt per class, as ResultMerge_multi_process.mergesingle writes them for mergebyrec: scenes in call order,
+    each scene's boxes in keep order, `name + " " + str(score) + " " + " ".join(map(str, [xmin, ymin, xmax, ymax]))`.
+    results: detect_scenes(..., tasks=("task1", "task2"))."""
+    if any("task2" not in r for r in results):
+        raise ValueError("write_task2_merged: the results hold no \"task2\" entry (detect_scenes(..., tasks=(\"task1\", \"task2\")))")
+    os.makedirs(dst, exist_ok=True)
+    host = []
+    for r in results:
+        t = r["task2"]
+        host.append((t["boxes"].cpu().numpy().astype(np.float64), t["scores"].cpu().numpy().astype(np.float64),
+                     t["labels"].cpu().numpy()))
+    for c, cname in enumerate(classnames):
+        with open(os.path.join(dst, "Task2_%s.txt" % cname), "w") as f:
+            for name, (boxes, scores, labels) in zip(scene_names, host):
+                for i in np.nonzero(labels == c)[0]:
+                    f.write(name + " " + str(float(scores[i])) + " " + " ".join(map(str, boxes[i].tolist())) + "\n")

@@ -75,6 +75,20 @@ int dafne_poly_nms_f64_batched_hip(const double* d_dets9, const int32_t* d_count
                                    void* d_ws, size_t ws_bytes, int flags, void* stream);
 
 /*
+ * Horizontal-box NMS of the tile merge for DOTA Task2 (dafne/utils/ResultMerge_multi_process.py:124-155 py_cpu_nms, the NMS
+ * mergebyrec :238-248 hands to mergebase; tools/prepare_dota/ResultMerge.py has the same file).  Rows are FLOAT64
+ * [x1, y1, x2, y2, score]; area = (x2 - x1 + 1) * (y2 - y1 + 1); for a kept row i and a later row j
+ * w = max(0, min(x2_i, x2_j) - max(x1_i, x1_j) + 1), h likewise, inter = w * h, ovr = inter / (area_i + area_j - inter),
+ * fp64 in that operation order; j survives iff ovr <= thresh (a NaN suppresses, as np.where(ovr <= thresh) leaves it out).
+ * order = argsort(score, stable)[::-1], as dafne_poly_nms_f64_batched_hip.
+ * d_dets5 [n_images][m_cap][5] doubles, d_counts [n_images] or NULL (= m_cap rows each); d_keep [n_images][m_cap] original
+ * row indices in descending-score order, d_num_keep [n_images].  m_cap <= 65536.
+ */
+size_t dafne_hbb_nms_f64_workspace_bytes(int n_images, int m_cap);
+int dafne_hbb_nms_f64_batched_hip(const double* d_dets5, const int32_t* d_counts, int n_images, int m_cap, double thresh,
+                                  int64_t* d_keep, int32_t* d_num_keep, void* d_ws, size_t ws_bytes, void* stream);
+
+/*
  * Greedy polygon NMS, the replacement for poly_nms.poly_gpu_nms (nms.py:91).
  *   d_dets9   [M,9] float32, C-contiguous: 8 corner coordinates + score
  *   thresh    a box is suppressed iff IoU(kept, box) > thresh (fp64 compare)
@@ -600,6 +614,17 @@ int dafne_scene_merge_rows_hip(const float* d_rows, const int32_t* d_counts, int
                                int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream);
 
 /*
+ * The same tile detections as the rows of the Task2 merge (ResultMerge_multi_process.py:238-248 mergebyrec): arguments, bucket
+ * order, skip mask, score mode, d_bucket_counts, d_src and the two-call protocol of dafne_scene_merge_rows_hip (same
+ * workspace size).  d_dets5 [n_buckets, m_cap, 5] f64: xmin, ymin, xmax, ymax, score with xmin = the minimum of the Task1
+ * row's four x values (rint(double(v) * 100) / 100 + left), ymin / xmax / ymax likewise -- dafne/utils/dota_utils.py:109-127
+ * (dots4ToRec4, parse_dota_rec) -- and the Task1 row's score.
+ */
+int dafne_scene_merge_hbb_rows_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap, const int32_t* d_tile_info,
+                                   int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap, double* d_dets5,
+                                   int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream);
+
+/*
  * TTA views cut straight from the scenes (DotaDatasetMapperTTA, dafne/modeling/tta.py:71-99: per TEST.AUG size, plain /
  * hflip / vflip).  View v = Pillow's BILINEAR resize of the win_h x win_w window of its source at (left, up) to
  * out_h x out_w, then the flips; window pixels past the source read as 0 (the split's padding=True).  Bit for bit
@@ -669,6 +694,15 @@ int dafne_tta_candidates_hip(const dafne_tta_view* views, int n_views, int n_ima
  */
 int dafne_scene_match_hip(const double* d_dets, const int32_t* d_bucket, int n, const double* d_gt, const int32_t* d_gt_offsets,
                           int n_buckets, int n_gt, double* d_ovmax, int32_t* d_jmax, void* stream);
+/*
+ * dafne_scene_match_hbb_hip: the Task2 (horizontal box) form of dafne_scene_match_hip.  d_dets [n, 4] and d_gt [n_gt, 4] f64
+ * are xmin, ymin, xmax, ymax (dota_utils.py:109-127 dots4ToRec4 of the oriented boxes); ov against EVERY box of the bucket is
+ * inters / uni of dafne/evaluation/voc_eval.py:158-173 applied to the two rectangles (+1 on widths, heights and both areas,
+ * fp64, that operation order).  d_ovmax[d] = the maximum over the bucket (zeros included), d_jmax[d] = the lowest index inside
+ * the bucket among the maxima; an empty bucket or one outside [0, n_buckets): -inf and -1.  Marking: dafne_scene_mark_hip.
+ */
+int dafne_scene_match_hbb_hip(const double* d_dets, const int32_t* d_bucket, int n, const double* d_gt, const int32_t* d_gt_offsets,
+                              int n_buckets, int n_gt, double* d_ovmax, int32_t* d_jmax, void* stream);
 size_t dafne_scene_mark_workspace_bytes(int n_gt);
 int dafne_scene_mark_hip(const int32_t* d_rank, const double* d_ovmax, const int32_t* d_jmax, const int32_t* d_bucket, int n,
                          const int32_t* d_gt_offsets, int n_buckets, const uint8_t* d_difficult, int n_gt, double thresh,

@@ -83,6 +83,9 @@ def parse_args(argv=None):
                     help="with --scene-dir: the scenes' labelTxt directory (<scene>.txt per scene, the val split): score the merged "
                          "detections against them on the device (VOC07 AP per class at TEST.IOU_TH), print the table and write "
                          "results.txt beside Task1_merged/")
+    ap.add_argument("--task2", action="store_true",
+                    help="with --scene-dir: also merge the same tile detections as horizontal boxes (DOTA Task2, mergebyrec): writes "
+                         "Task2_merged/Task2_<class>.txt, with --zip task2_merged.zip, with --scene-labels results_task2.txt")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides")
     return ap.parse_args(argv)
 
@@ -121,6 +124,8 @@ def scene_args_error(args):
         return "--scene-tta needs --scene-dir (it augments the tiles of whole scenes; --tta takes --image-dir)"
     if args.scene_labels and not args.scene_dir:
         return "--scene-labels needs --scene-dir (it scores whole-scene detections; --dataset-name scores tile detections)"
+    if args.task2 and not args.scene_dir:
+        return "--task2 needs --scene-dir (the horizontal-box merge runs on whole-scene detections)"
     if not args.scene_dir:
         return None
     if args.num_gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -130,12 +135,13 @@ def scene_args_error(args):
     return None
 
 
-def write_zip(output_dir, merged_dir):
-    """dota_evaluation.create_zip: task1_merged.zip with the Task1_*.txt files of merged_dir at the archive's root."""
+def write_zip(output_dir, merged_dir, task="Task1"):
+    """dota_evaluation.create_zip: task1_merged.zip with the Task1_*.txt files of merged_dir at the archive's root (task
+    "Task2": task2_merged.zip with the Task2_*.txt files)."""
     import glob
     import zipfile
-    with zipfile.ZipFile(os.path.join(output_dir, "task1_merged.zip"), mode="w", compression=zipfile.ZIP_DEFLATED) as z:
-        for fname in glob.glob(merged_dir + "/Task1_*.txt"):
+    with zipfile.ZipFile(os.path.join(output_dir, "%s_merged.zip" % task.lower()), mode="w", compression=zipfile.ZIP_DEFLATED) as z:
+        for fname in glob.glob(merged_dir + "/%s_*.txt" % task):
             z.write(fname, arcname=os.path.basename(fname))
 
 
@@ -151,7 +157,7 @@ def run_scenes(args):
     from dafne_amd.data.loader import read_image
     from dafne_amd.evaluation import dota_evaluation as de
     from dafne_amd.registry import build_model
-    from dafne_amd.scene import write_task1_merged
+    from dafne_amd.scene import write_task1_merged, write_task2_merged
     from dafne_amd.utils.host import usable_cpus
 
     cfg = load_cfg(args.config_file, args.opts)
@@ -179,7 +185,8 @@ def run_scenes(args):
         runner = OneStageRCNNWithTTA(cfg, model)
     else:
         runner = model
-    res = runner.detect_scenes(scenes, patch_size=args.patch_size, overlap=args.overlap, batch=args.scene_batch)
+    res = runner.detect_scenes(scenes, patch_size=args.patch_size, overlap=args.overlap, batch=args.scene_batch,
+                               tasks=("task1", "task2") if args.task2 else ("task1",))
     names = [r["image_id"] for r in records]
     classnames = (list(de.CLASSNAMES_DOTA_1_0) + ["container-crane"])[:cfg.MODEL.DAFNE.NUM_CLASSES]
     out = args.task1_merged_dir or os.path.join(cfg.OUTPUT_DIR, "scenes")
@@ -192,6 +199,12 @@ def run_scenes(args):
     for n, r, s in zip(names, res, scenes):
         print("scene %s (%dx%d, %d tiles): %d detections" % (n, s.shape[0], s.shape[1], len(r["origins"]), len(r["scores"])))
     print("Task1_merged written to %s" % merged)
+    if args.task2:
+        merged2 = os.path.join(out, "Task2_merged")
+        write_task2_merged(res, names, classnames, merged2)
+        if args.zip:
+            write_zip(out, merged2, "Task2")
+        print("Task2_merged written to %s (%d horizontal boxes)" % (merged2, sum(len(r["task2"]["scores"]) for r in res)))
     if args.scene_labels:
         from dafne_amd.evaluation.scene_eval import load_scene_labels
         labels = load_scene_labels(args.scene_labels, names, classnames)
@@ -199,6 +212,11 @@ def run_scenes(args):
         for k, v in scored["task1"].items():
             print(f"{k: <18}: {v:2.4f}")
         print("results.txt written to %s" % out)
+        if args.task2:
+            scored2 = runner.score_scenes(res, labels, classnames, output_folder=out, task="task2")
+            for k, v in scored2["task2"].items():
+                print(f"{k: <18}: {v:2.4f}")
+            print("results_task2.txt written to %s" % out)
     return res
 
 
