@@ -46,6 +46,14 @@ class ViewSrc(ctypes.Structure):
                 ("win_h", c_i32), ("win_w", c_i32), ("hflip", c_i32), ("vflip", c_i32), ("reserved", c_i32)]
 
 
+class ScaledTile(ctypes.Structure):
+    _fields_ = [("d_scene", c_void_p), ("h", c_i32), ("w", c_i32), ("layout_hwc", c_i32), ("new_h", c_i32), ("new_w", c_i32),
+                ("left", c_i32), ("up", c_i32), ("filter", c_i32)]
+
+
+FILTER_BILINEAR, FILTER_BICUBIC = 0, 1           # dafne_scaled_tile.filter (include/dafne_amd.h)
+
+
 class TtaView(ctypes.Structure):
     _fields_ = [("d_rows", c_void_p), ("d_count", c_void_p), ("tile", c_i32), ("slot", c_i32), ("flip_x", c_i32),
                 ("flip_y", c_i32), ("width", c_float), ("height", c_float), ("rx1", c_float), ("ry1", c_float), ("rx2", c_float),
@@ -162,6 +170,14 @@ SIGNATURES = {
                                                c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dafne_scene_views_workspace_bytes": (c_size_t, [ctypes.POINTER(ViewSrc), c_int, c_int, c_int]),
     "dafne_scene_views_u8_hip": (c_int, [ctypes.POINTER(ViewSrc), c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dafne_scene_scaled_tiles_workspace_bytes": (c_size_t, [ctypes.POINTER(ScaledTile), c_int]),
+    "dafne_scene_scaled_tiles_u8_hip": (c_int, [ctypes.POINTER(ScaledTile), c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dafne_scene_merge_rows_scaled_hip": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                                  ctypes.c_uint64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                  c_void_p]),
+    "dafne_scene_merge_hbb_rows_scaled_hip": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                                      ctypes.c_uint64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_size_t, c_void_p]),
     "dafne_tta_candidates_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dafne_tta_candidates_hip": (c_int, [ctypes.POINTER(TtaView), c_int, c_int, c_int, c_int] + [c_void_p] * 10 + [c_size_t, c_void_p]),
     "dafne_scene_match_hip": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

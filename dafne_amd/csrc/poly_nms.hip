@@ -2053,7 +2053,7 @@ int dafne_hbb_nms_f64_batched_hip(const double* d_dets5, const int32_t* d_counts
 // rows dafne_poly_nms_f64_batched_hip takes, bit for bit what the text route parses:
 //   coordinate q = rint(double(v) * 100) / 100   == float("%.2f" % v)   (the product is exact, rint rounds half to even,
 //   score      q = rint(double(v) * 1e4) / 1e4   == float("%.4f" % v)    the division is correctly rounded)
-// then (q + left | up) / 1.0.  One bucket per (scene, class), in tile order and then the tile's row order: a count, an ordered
+// then (q + left | up) / rate (poly2origpoly; 1.0 unless the tile comes from a resampled scene).  One bucket per (scene, class), in tile order and then the tile's row order: a count, an ordered
 // scan and ballot ranks -- no atomic decides a position.  (This unit is built with -ffp-contract=off.)
 namespace {
 
@@ -2110,7 +2110,8 @@ __device__ __forceinline__ double quantise(float v, double scale) {
 // quantised, shifted coordinates: xmin, ymin, xmax, ymax) + the same score -- the Task2 row of mergebyrec.
 template <int ROW>
 __global__ void __launch_bounds__(kMergeThreads) merge_write_kernel(const float* __restrict__ rows, const int32_t* __restrict__ counts,
-                                                                    int k_cap, const int32_t* __restrict__ tile_info, int n_scenes,
+                                                                    int k_cap, const int32_t* __restrict__ tile_info,
+                                                                    const double* __restrict__ tile_scale, int n_scenes,
                                                                     int n_classes,
                                                                     unsigned long long skip, int score_mode,
                                                                     const int32_t* __restrict__ offs, int m_cap,
@@ -2121,6 +2122,7 @@ __global__ void __launch_bounds__(kMergeThreads) merge_write_kernel(const float*
     const int t = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int left = tile_info[3 * t], up = tile_info[3 * t + 1], s = tile_info[3 * t + 2];
+    const double rate = tile_scale ? tile_scale[t] : 1.0;      // the split rate of the tile's scene
     if (s < 0 || s >= n_scenes) return;                // (block-uniform) a tile of no scene of this call has no bucket
     if (threadIdx.x < n_classes) base[threadIdx.x] = offs[(size_t)t * n_classes + threadIdx.x];
     int n = counts[t];
@@ -2149,7 +2151,7 @@ __global__ void __launch_bounds__(kMergeThreads) merge_write_kernel(const float*
                 double* d = dets + (o * m_cap + pos) * ROW;
                 double q[8];
 #pragma unroll
-                for (int k = 0; k < 8; k++) q[k] = (quantise(row[k], 100.0) + (double)((k & 1) ? up : left)) / 1.0;
+                for (int k = 0; k < 8; k++) q[k] = (quantise(row[k], 100.0) + (double)((k & 1) ? up : left)) / rate;
                 if (ROW == 9) {
 #pragma unroll
                     for (int k = 0; k < 8; k++) d[k] = q[k];
@@ -2189,8 +2191,8 @@ size_t dafne_scene_merge_workspace_bytes(int n_tiles, int n_classes) {
 
 // both merges: row_w 9 = the Task1 rows, 5 = the Task2 rows (same hist, scan and workspace)
 static int scene_merge_rows(const char* what, int row_w, const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap,
-                            const int32_t* d_tile_info, int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap,
-                            double* d_dets, int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
+                            const int32_t* d_tile_info, const double* d_tile_scale, int n_scenes, int n_classes, uint64_t skip_mask,
+                            int score_mode, int m_cap, double* d_dets, int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
     if (!d_rows || !d_counts || !d_tile_info || !d_bucket_counts || !d_ws || n_tiles < 1 || k_cap < 1 || n_scenes < 1 ||
         m_cap < 0 || (score_mode != 0 && score_mode != 1))
         return dafne::fail(DAFNE_E_INVALID, "%s: bad args (n_tiles %d, k_cap %d, n_scenes %d, m_cap %d, score_mode %d)", what,
@@ -2218,25 +2220,41 @@ static int scene_merge_rows(const char* what, int row_w, const float* d_rows, co
     if (rc || m_cap == 0) return rc;
     if (row_w == 9)
         hipLaunchKernelGGL(merge_write_kernel<9>, dim3(n_tiles), dim3(kMergeThreads), 0, st, d_rows, d_counts, k_cap, d_tile_info,
-                           n_scenes, n_classes, (unsigned long long)skip_mask, score_mode, offs, m_cap, d_dets, d_src);
+                           d_tile_scale, n_scenes, n_classes, (unsigned long long)skip_mask, score_mode, offs, m_cap, d_dets, d_src);
     else
         hipLaunchKernelGGL(merge_write_kernel<5>, dim3(n_tiles), dim3(kMergeThreads), 0, st, d_rows, d_counts, k_cap, d_tile_info,
-                           n_scenes, n_classes, (unsigned long long)skip_mask, score_mode, offs, m_cap, d_dets, d_src);
+                           d_tile_scale, n_scenes, n_classes, (unsigned long long)skip_mask, score_mode, offs, m_cap, d_dets, d_src);
     return dafne::check_launch("scene_merge_write");
 }
 
 int dafne_scene_merge_rows_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap, const int32_t* d_tile_info,
                                int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap, double* d_dets,
                                int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
-    return scene_merge_rows("scene_merge_rows", 9, d_rows, d_counts, n_tiles, k_cap, d_tile_info, n_scenes, n_classes, skip_mask,
-                            score_mode, m_cap, d_dets, d_bucket_counts, d_src, d_ws, ws_bytes, stream);
+    return scene_merge_rows("scene_merge_rows", 9, d_rows, d_counts, n_tiles, k_cap, d_tile_info, nullptr, n_scenes, n_classes,
+                            skip_mask, score_mode, m_cap, d_dets, d_bucket_counts, d_src, d_ws, ws_bytes, stream);
 }
 
 int dafne_scene_merge_hbb_rows_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap, const int32_t* d_tile_info,
                                    int n_scenes, int n_classes, uint64_t skip_mask, int score_mode, int m_cap, double* d_dets5,
                                    int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
-    return scene_merge_rows("scene_merge_hbb_rows", 5, d_rows, d_counts, n_tiles, k_cap, d_tile_info, n_scenes, n_classes,
+    return scene_merge_rows("scene_merge_hbb_rows", 5, d_rows, d_counts, n_tiles, k_cap, d_tile_info, nullptr, n_scenes, n_classes,
                             skip_mask, score_mode, m_cap, d_dets5, d_bucket_counts, d_src, d_ws, ws_bytes, stream);
+}
+
+int dafne_scene_merge_rows_scaled_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap,
+                                      const int32_t* d_tile_info, const double* d_tile_scale, int n_scenes, int n_classes,
+                                      uint64_t skip_mask, int score_mode, int m_cap, double* d_dets, int32_t* d_bucket_counts,
+                                      int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
+    return scene_merge_rows("scene_merge_rows_scaled", 9, d_rows, d_counts, n_tiles, k_cap, d_tile_info, d_tile_scale, n_scenes,
+                            n_classes, skip_mask, score_mode, m_cap, d_dets, d_bucket_counts, d_src, d_ws, ws_bytes, stream);
+}
+
+int dafne_scene_merge_hbb_rows_scaled_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap,
+                                          const int32_t* d_tile_info, const double* d_tile_scale, int n_scenes, int n_classes,
+                                          uint64_t skip_mask, int score_mode, int m_cap, double* d_dets5,
+                                          int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream) {
+    return scene_merge_rows("scene_merge_hbb_rows_scaled", 5, d_rows, d_counts, n_tiles, k_cap, d_tile_info, d_tile_scale, n_scenes,
+                            n_classes, skip_mask, score_mode, m_cap, d_dets5, d_bucket_counts, d_src, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

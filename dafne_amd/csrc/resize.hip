@@ -12,6 +12,8 @@
 // operations as the C code).  Horizontal / vertical flips of the TTA views are folded into the store index.
 #include "common.h"
 
+#include <string.h>
+
 namespace {
 
 constexpr int kPrec = 22;      // PRECISION_BITS = 32 - 8 - 2
@@ -22,11 +24,23 @@ struct Taps {
     int k[kMaxTaps];
 };
 
-// coefficients of output index i for an axis of in_size -> out_size samples
+constexpr int kBilinear = 0, kBicubic = 1;      // dafne_scaled_tile.filter
+
+// Pillow's filter functions (Resample.c bilinear_filter / bicubic_filter with a = -0.5), a >= 0
+template <int F>
+__device__ __forceinline__ double filter_weight(double a) {
+    if (F == kBilinear) return a < 1.0 ? 1.0 - a : 0.0;
+    if (a < 1.0) return ((-0.5 + 2.0) * a - (-0.5 + 3.0)) * a * a + 1;
+    if (a < 2.0) return (((a - 5) * a + 8) * a - 4) * -0.5;
+    return 0.0;
+}
+
+// coefficients of output index i for an axis of in_size -> out_size samples; F: the filter (support 1 / 2)
+template <int F>
 __device__ __forceinline__ void taps_for(int i, int in_size, int out_size, Taps& t) {
     const double scale = (double)(float)in_size / out_size;      // box = (0, in_size) as floats
     const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * filterscale;
+    const double support = (F == kBilinear ? 1.0 : 2.0) * filterscale;
     const double center = 0.0 + (i + 0.5) * scale;
     const double ss = 1.0 / filterscale;
     int xmin = (int)(center - support + 0.5);
@@ -40,7 +54,7 @@ __device__ __forceinline__ void taps_for(int i, int in_size, int out_size, Taps&
     for (int x = 0; x < xmax; x++) {
         double a = (x + xmin - center + 0.5) * ss;
         if (a < 0.0) a = -a;
-        const double v = a < 1.0 ? 1.0 - a : 0.0;
+        const double v = filter_weight<F>(a);
         w[x] = v;
         ww += v;
     }
@@ -52,6 +66,8 @@ __device__ __forceinline__ void taps_for(int i, int in_size, int out_size, Taps&
     t.xmin = xmin;
     t.n = xmax;
 }
+
+__device__ __forceinline__ void taps_for(int i, int in_size, int out_size, Taps& t) { taps_for<kBilinear>(i, in_size, out_size, t); }
 
 __device__ __forceinline__ unsigned char clip8(int v) {
     v >>= kPrec;
@@ -263,6 +279,7 @@ struct ViewDev {
 
 struct AxisDev {
     int in_size, out_size;
+    int filter, reserved;                   // kBilinear / kBicubic
     size_t off;                             // int offset of the table in the coefficient area
 };
 
@@ -274,7 +291,10 @@ __global__ void __launch_bounds__(256) views_taps_kernel(const AxisDev* __restri
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ax.out_size) return;
     Taps t;
-    taps_for(i, ax.in_size, ax.out_size, t);
+    if (ax.filter == kBicubic)
+        taps_for<kBicubic>(i, ax.in_size, ax.out_size, t);
+    else
+        taps_for<kBilinear>(i, ax.in_size, ax.out_size, t);
     int* c = coef + ax.off + (size_t)i * kTapStride;
     c[0] = t.xmin;
     c[1] = t.n;
@@ -361,6 +381,7 @@ bool view_axes(const dafne_view_src* views, int n_views, int out_h, int out_w, A
                 if (na - first >= kViewMaxAxes) return false;
                 axes[na].in_size = in;
                 axes[na].out_size = pass ? out_h : out_w;
+                axes[na].filter = kBilinear;
                 na++;
             }
             (pass ? ty : tx)[v] = a;
@@ -377,8 +398,8 @@ bool view_axes(const dafne_view_src* views, int n_views, int out_h, int out_w, A
 
 // rows of the LDS intermediate a workgroup of `by` resampled rows needs, for the largest vertical scale of the launch:
 // the span ylo .. xmin + n of rows y0 .. y0 + by - 1 is at most (by - 1) * scale + 2 * support + 1 (taps_for's rounding)
-int view_rows_cap(double scale, int by, int in_max) {
-    const double support = scale < 1.0 ? 1.0 : scale;
+int view_rows_cap(double scale, int by, int in_max, double filter_support = 1.0) {
+    const double support = filter_support * (scale < 1.0 ? 1.0 : scale);
     int r = (int)((by - 1) * scale + 2.0 * support + 1.0) + 2;
     return r < in_max ? r : in_max;
 }
@@ -466,6 +487,253 @@ int dafne_scene_views_u8_hip(const dafne_view_src* views, int n_views, int out_h
     hipLaunchKernelGGL(views_kernel, dim3((out_w + kViewBX - 1) / kViewBX, (out_h + by - 1) / by, gz), dim3(256),
                        (size_t)3 * kViewBX * rows_cap, st, d_views, n_views, d_axes, d_coef, out_h, out_w, by, rows_cap, d_out);
     return dafne::check_launch("scene_views");
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------- tiles of a resampled scene
+// The split of a scene resampled to new_h x new_w (multi-scale whole-scene inference): tile t is the patch x patch crop at
+// (left, up) of Pillow's resize of the WHOLE scene with its filter (the taps clip at the scene's border, not at the tile's),
+// zero past new_h / new_w -- cut straight from the original scene.  views_kernel's structure: one coefficient table per distinct
+// (in size, out size, filter) axis of the call (views_taps_kernel), a workgroup owns kViewBX columns x `by` rows of one tile,
+// runs the horizontal pass into LDS for the source rows its vertical taps touch (clip8 after it, as Pillow's uint8 intermediate:
+// bicubic coefficients are negative), then the vertical pass from LDS into an LDS copy of its output rows, which leaves as
+// 4-byte words.  The resampled scene itself never exists in memory.
+namespace {
+
+constexpr int kTileStore = 4;               // bytes per store: patch * 3 and kViewBX * 3 are multiples of it
+
+struct ScaledDev {
+    dafne_scaled_tile s;
+    int tx, ty;                             // coefficient table of the x / y axis
+};
+
+__global__ void __launch_bounds__(256) scaled_tiles_kernel(const ScaledDev* __restrict__ tiles, int n_tiles,
+                                                           const AxisDev* __restrict__ axes, const int* __restrict__ coef, int patch,
+                                                           int by, int rows_cap, uint8_t* __restrict__ out) {
+    extern __shared__ uint8_t tmp[];         // [3][rows_cap][kViewBX], then the output rows [by][kViewBX * 3]
+    uint8_t* obuf = tmp + (size_t)3 * rows_cap * kViewBX;
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * kViewBX, y0 = blockIdx.y * by;
+    const int bw = min(kViewBX, patch - x0), bh = min(by, patch - y0);       // the block's share of the tile
+    for (int v = blockIdx.z; v < n_tiles; v += gridDim.z) {
+        const ScaledDev td = tiles[v];
+        const dafne_scaled_tile& s = td.s;
+        const int X0 = s.left + x0, Y0 = s.up + y0;                          // resampled coordinates of the block
+        const int nx = max(0, min(bw, s.new_w - X0)), ny = max(0, min(bh, s.new_h - Y0));
+        const bool any = nx > 0 && ny > 0;                                   // (block-uniform)
+        const int* cx = coef + axes[td.tx].off;
+        const int* cy = coef + axes[td.ty].off;
+        int ylo = 0;
+        if (any) {
+            // source rows of the block's vertical taps: xmin is non-decreasing in the output index, and so is xmin + n
+            ylo = cy[(size_t)Y0 * kTapStride];
+            const int* clast = cy + (size_t)(Y0 + ny - 1) * kTapStride;
+            const int nrows = min(clast[0] + clast[1] - ylo, rows_cap);
+            const size_t plane = (size_t)s.h * s.w;
+            for (int e = tid; e < nrows * kViewBX; e += blockDim.x) {
+                const int r = e / kViewBX, c = e - r * kViewBX;
+                if (c >= nx) continue;
+                const int* t = cx + (size_t)(X0 + c) * kTapStride;
+                const int xmin = t[0], n = t[1];
+                const size_t p = (size_t)(ylo + r) * s.w + xmin;             // taps stay inside the scene: no bounds test
+                int a0 = 1 << (kPrec - 1), a1 = a0, a2 = a0;
+                if (s.layout_hwc) {
+                    const uint8_t* src = s.d_scene + p * 3;
+                    for (int x = 0; x < n; x++) {
+                        const int k = t[2 + x];
+                        a0 += (int)src[3 * x] * k;
+                        a1 += (int)src[3 * x + 1] * k;
+                        a2 += (int)src[3 * x + 2] * k;
+                    }
+                } else {
+                    const uint8_t* src = s.d_scene + p;
+                    for (int x = 0; x < n; x++) {
+                        const int k = t[2 + x];
+                        a0 += (int)src[x] * k;
+                        a1 += (int)src[plane + x] * k;
+                        a2 += (int)src[2 * plane + x] * k;
+                    }
+                }
+                tmp[(0 * rows_cap + r) * kViewBX + c] = clip8(a0);
+                tmp[(1 * rows_cap + r) * kViewBX + c] = clip8(a1);
+                tmp[(2 * rows_cap + r) * kViewBX + c] = clip8(a2);
+            }
+        }
+        __syncthreads();
+        // vertical pass into the output rows; zero past the resampled scene
+        for (int e = tid; e < bh * kViewBX; e += blockDim.x) {
+            const int yl = e / kViewBX, c = e - yl * kViewBX;
+            if (c >= bw) continue;
+            uint8_t b0 = 0, b1 = 0, b2 = 0;
+            if (c < nx && yl < ny) {
+                const int* t = cy + (size_t)(Y0 + yl) * kTapStride;
+                const int r0 = t[0] - ylo, n = t[1];
+                int a0 = 1 << (kPrec - 1), a1 = a0, a2 = a0;
+                for (int y = 0; y < n; y++) {
+                    const int k = t[2 + y];
+                    const int r = r0 + y < rows_cap ? r0 + y : rows_cap - 1;     // (never clamps: rows_cap bounds the span)
+                    a0 += (int)tmp[(0 * rows_cap + r) * kViewBX + c] * k;
+                    a1 += (int)tmp[(1 * rows_cap + r) * kViewBX + c] * k;
+                    a2 += (int)tmp[(2 * rows_cap + r) * kViewBX + c] * k;
+                }
+                b0 = clip8(a0);
+                b1 = clip8(a1);
+                b2 = clip8(a2);
+            }
+            uint8_t* o = obuf + (yl * kViewBX + c) * 3;
+            o[0] = b0;
+            o[1] = b1;
+            o[2] = b2;
+        }
+        __syncthreads();
+        // the block's bw * 3 bytes of every row: byte offset ((v * patch + y) * patch + x0) * 3 is a multiple of 4
+        const int wpr = bw * 3 / kTileStore;
+        for (int e = tid; e < bh * wpr; e += blockDim.x) {
+            const int yl = e / wpr, q = e - yl * wpr;
+            uint32_t* dst = reinterpret_cast<uint32_t*>(out + (((size_t)v * patch + y0 + yl) * patch + x0) * 3);
+            dst[q] = reinterpret_cast<const uint32_t*>(obuf + yl * kViewBX * 3)[q];
+        }
+        __syncthreads();
+    }
+}
+
+struct ScaledPlan {
+    AxisDev* axes;          // 2 * n_tiles at most
+    int* tx;
+    int* ty;
+    int n_axes;
+    size_t coef_ints;
+};
+
+// the distinct (in size, out size, filter) axes of a call; tx / ty: per tile its tables.  The caller owns the arrays.
+void scaled_axes(const dafne_scaled_tile* tiles, int n_tiles, ScaledPlan& p) {
+    int na = 0;
+    for (int v = 0; v < n_tiles; v++)
+        for (int pass = 0; pass < 2; pass++) {
+            const int in = pass ? tiles[v].h : tiles[v].w, o = pass ? tiles[v].new_h : tiles[v].new_w, f = tiles[v].filter;
+            int a = 0;
+            // consecutive tiles share their scene and scale: look at the latest tables first
+            for (a = na - 1; a >= 0; a--)
+                if (p.axes[a].in_size == in && p.axes[a].out_size == o && p.axes[a].filter == f) break;
+            if (a < 0) {
+                a = na++;
+                p.axes[a].in_size = in;
+                p.axes[a].out_size = o;
+                p.axes[a].filter = f;
+                p.axes[a].reserved = 0;
+            }
+            (pass ? p.ty : p.tx)[v] = a;
+        }
+    size_t off = 0;
+    for (int a = 0; a < na; a++) {
+        p.axes[a].off = off;
+        off += (size_t)p.axes[a].out_size * kTapStride;
+    }
+    p.n_axes = na;
+    p.coef_ints = off;
+}
+
+bool scaled_tile_ok(const dafne_scaled_tile& d) {
+    return d.d_scene && d.h >= 1 && d.w >= 1 && (d.layout_hwc == 0 || d.layout_hwc == 1) && d.new_h >= 1 && d.new_w >= 1 &&
+           d.left >= 0 && d.up >= 0 && d.left < d.new_w && d.up < d.new_h && (d.filter == kBilinear || d.filter == kBicubic);
+}
+
+size_t scaled_tiles_bytes(int n_tiles) { return dafne::align_up(sizeof(ScaledDev) * (size_t)n_tiles, 256); }
+size_t scaled_axes_bytes(int n_axes) { return dafne::align_up(sizeof(AxisDev) * (size_t)n_axes, 256); }
+
+}  // namespace
+
+extern "C" {
+
+size_t dafne_scene_scaled_tiles_workspace_bytes(const dafne_scaled_tile* tiles, int n_tiles) {
+    if (!tiles || n_tiles < 1) return 0;
+    for (int v = 0; v < n_tiles; v++)
+        if (!scaled_tile_ok(tiles[v])) return 0;
+    ScaledPlan p;
+    p.axes = new AxisDev[2 * (size_t)n_tiles];
+    p.tx = new int[n_tiles];
+    p.ty = new int[n_tiles];
+    scaled_axes(tiles, n_tiles, p);
+    delete[] p.axes;
+    delete[] p.tx;
+    delete[] p.ty;
+    return scaled_tiles_bytes(n_tiles) + scaled_axes_bytes(p.n_axes) + dafne::align_up(p.coef_ints * sizeof(int), 256);
+}
+
+int dafne_scene_scaled_tiles_u8_hip(const dafne_scaled_tile* tiles, int n_tiles, int patch, uint8_t* d_out_hwc, void* d_ws,
+                                    size_t ws_bytes, void* stream) {
+    if (!tiles || !d_out_hwc || !d_ws || n_tiles < 1 || patch < kTileStore)
+        return dafne::fail(DAFNE_E_INVALID, "scene_scaled_tiles: bad args (n_tiles %d, patch %d)", n_tiles, patch);
+    if (patch % kTileStore)
+        return dafne::fail(DAFNE_E_UNSUPPORTED, "scene_scaled_tiles: patch %d is not a multiple of %d", patch, kTileStore);
+    int omax = 1;
+    for (int v = 0; v < n_tiles; v++) {
+        const dafne_scaled_tile& d = tiles[v];
+        if (!scaled_tile_ok(d))
+            return dafne::fail(DAFNE_E_INVALID, "scene_scaled_tiles: tile %d: scene %dx%d layout %d -> %dx%d origin (%d, %d) filter %d", v,
+                               d.h, d.w, d.layout_hwc, d.new_h, d.new_w, d.left, d.up, d.filter);
+        // tap count of the widest filter: 2 * ceil(support) + 1, support = (1 | 2) * max(scale, 1)
+        const double fs = d.filter == kBicubic ? 2.0 : 1.0;
+        const double sx = (double)d.w / d.new_w, sy = (double)d.h / d.new_h;
+        if (fs * (sx > 1 ? sx : 1) * 2 + 2 > kMaxTaps || fs * (sy > 1 ? sy : 1) * 2 + 2 > kMaxTaps)
+            return dafne::fail(DAFNE_E_UNSUPPORTED, "scene_scaled_tiles: tile %d: %s downscale factor above %d", v,
+                               d.filter == kBicubic ? "bicubic" : "bilinear", (int)((kMaxTaps / 2 - 1) / fs));
+        if (d.new_h > omax) omax = d.new_h;
+        if (d.new_w > omax) omax = d.new_w;
+    }
+    const size_t need = dafne_scene_scaled_tiles_workspace_bytes(tiles, n_tiles);
+    if (ws_bytes < need) return dafne::fail(DAFNE_E_WORKSPACE, "scene_scaled_tiles: workspace %zu < %zu", ws_bytes, need);
+    ScaledPlan p;
+    p.axes = new AxisDev[2 * (size_t)n_tiles];
+    p.tx = new int[n_tiles];
+    p.ty = new int[n_tiles];
+    scaled_axes(tiles, n_tiles, p);
+    // header: tiles + axis tables, one copy
+    const size_t tbytes = scaled_tiles_bytes(n_tiles), hdr = tbytes + scaled_axes_bytes(p.n_axes);
+    uint8_t* blob = new uint8_t[hdr]();
+    ScaledDev* td = reinterpret_cast<ScaledDev*>(blob);
+    for (int v = 0; v < n_tiles; v++) {
+        td[v].s = tiles[v];
+        td[v].tx = p.tx[v];
+        td[v].ty = p.ty[v];
+    }
+    memcpy(blob + tbytes, p.axes, sizeof(AxisDev) * (size_t)p.n_axes);
+    const int na = p.n_axes;
+    delete[] p.axes;
+    delete[] p.tx;
+    delete[] p.ty;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t ce = hipMemcpyAsync(d_ws, blob, hdr, hipMemcpyHostToDevice, st);
+    delete[] blob;
+    if (ce != hipSuccess) return dafne::fail(DAFNE_E_HIP, "scene_scaled_tiles: hipMemcpyAsync: %s", hipGetErrorString(ce));
+    const ScaledDev* d_tiles = (const ScaledDev*)d_ws;
+    const AxisDev* d_axes = (const AxisDev*)((uint8_t*)d_ws + tbytes);
+    int* d_coef = (int*)((uint8_t*)d_ws + hdr);
+    for (int a0 = 0; a0 < na; a0 += 65535) {
+        const int n = na - a0 < 65535 ? na - a0 : 65535;
+        hipLaunchKernelGGL(views_taps_kernel, dim3((omax + 255) / 256, n), dim3(256), 0, st, d_axes + a0, n, d_coef);
+        const int rc = dafne::check_launch("scene_scaled_tiles_taps");
+        if (rc) return rc;
+    }
+    // rows per workgroup: the most that keep the LDS intermediate and the output rows within the budget
+    int by = 32 < patch ? 32 : patch, rows_cap = 0;
+    for (;;) {
+        rows_cap = 1;
+        for (int v = 0; v < n_tiles; v++) {
+            const dafne_scaled_tile& d = tiles[v];
+            const int r = view_rows_cap((double)d.h / d.new_h, by, d.h, d.filter == kBicubic ? 2.0 : 1.0);
+            if (r > rows_cap) rows_cap = r;
+        }
+        if (by == 1 || 3 * kViewBX * (rows_cap + by) <= kViewLdsBudget) break;
+        by /= 2;
+    }
+    const size_t lds = (size_t)3 * kViewBX * (rows_cap + by);
+    if (lds > 64 * 1024) return dafne::fail(DAFNE_E_UNSUPPORTED, "scene_scaled_tiles: %d source rows per output row", rows_cap);
+    const unsigned gz = (unsigned)(n_tiles < 65535 ? n_tiles : 65535);
+    hipLaunchKernelGGL(scaled_tiles_kernel, dim3((patch + kViewBX - 1) / kViewBX, (patch + by - 1) / by, gz), dim3(256), lds, st,
+                       d_tiles, n_tiles, d_axes, d_coef, patch, by, rows_cap, d_out_hwc);
+    return dafne::check_launch("scene_scaled_tiles");
 }
 
 }  // extern "C"

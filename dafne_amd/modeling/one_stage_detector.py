@@ -552,16 +552,19 @@ class OneStageDetector(nn.Module):
                 t.record_stream(main)
             return res
 
-    def detect_scenes(self, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",)):
+    def detect_scenes(self, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",), scales=(1,),
+                      resample="bicubic"):
         """Whole scenes in, scene-coordinate detections out: the reference's split_dota.py (rate 1) + tile inference + the tile
         merge (mergebypoly) in one call, on the device (dafne_amd/scene.py).  scenes: device uint8 BGR [H,W,3] or [3,H,W]
         images.  -> one dict per scene: corners [K,8] f64, scores [K] f64 (the merge's 4-decimal values), labels [K], tile /
         row (the tile row each detection came from), origins (the scene's tile origins); class by class, each in NMS keep
         order.  scene.write_task1_merged writes them as Task1_merged/ files.  tasks=("task1", "task2"): every dict also holds
-        "task2", the horizontal boxes merged from the same tile rows as mergebyrec merges them (scene.write_task2_merged)."""
+        "task2", the horizontal boxes merged from the same tile rows as mergebyrec merges them (scene.write_task2_merged).
+        scales=(1, 0.5): multi-scale -- every scene is also split after a Pillow `resample` resize by each scale and all its tiles
+        are merged in one NMS, in the scene's coordinates (scene.detect_scenes; the dicts gain "tile_scales")."""
         from .. import scene
         return scene.detect_scenes(self, scenes, patch_size=patch_size, overlap=overlap, batch=batch, layout_hwc=layout_hwc,
-                                   tasks=tasks)
+                                   tasks=tasks, scales=scales, resample=resample)
 
     def score_scenes(self, results, labels, classnames, output_folder=None, task="task1"):
         """detect_scenes' results against the scenes' labelTxt (evaluation.scene_eval.load_scene_labels), matched on the device:

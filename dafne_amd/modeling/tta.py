@@ -467,14 +467,15 @@ class OneStageRCNNWithTTA(nn.Module):
         r.pred_classes = torch.cat([i.pred_classes for i in insts], dim=0)
         return r
 
-    def detect_scenes(self, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",)):
+    def detect_scenes(self, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",), scales=(1,)):
         """OneStageDetector.detect_scenes with this wrapper's TTA on every tile (dafne_amd/scene.py, detect_scenes_tta): the
         released DOTA route -- split_dota.py, do_test_with_TTA on every tile, mergebypoly -- in one call.  Every tile's merged
         rows are this wrapper's result for that tile called alone; the views of `batch` tiles are cut in one launch per TTA size.
-        -> one dict per scene, as OneStageDetector.detect_scenes; "tile" / "row" index the tiles' merged TTA rows."""
+        -> one dict per scene, as OneStageDetector.detect_scenes; "tile" / "row" index the tiles' merged TTA rows.  scales other
+        than (1,) raise NotImplementedError (the views are cut from the scene itself)."""
         from .. import scene
         return scene.detect_scenes_tta(self, scenes, patch_size=patch_size, overlap=overlap, batch=batch, layout_hwc=layout_hwc,
-                                       tasks=tasks)
+                                       tasks=tasks, scales=scales)
 
     def score_scenes(self, results, labels, classnames, output_folder=None, task="task1"):
         """OneStageDetector.score_scenes for this wrapper's detect_scenes results."""

@@ -13,6 +13,8 @@ strict hull test).  write_task1_merged then writes what mergebypoly writes, byte
 
   split_origins(h, w, patch_size, overlap)      SplitSingle's tile origins at rate 1, in its emission order
   gather_tiles(scenes, origins, patch)          [T, patch, patch, 3] uint8 BGR tiles of all scenes, one launch
+  scaled_size(h, w, scale)                      the size of a scene resampled by `scale`
+  gather_scaled_tiles(scenes, scales, origins, patch)   the same tiles of the RESAMPLED scenes, cut from the scenes, one launch
   merge_tile_rows(...)                          tile rows -> per-(scene, class) f64 merge rows + back-index
   merge_scenes(...)                             the above + NMS + the kept rows per scene
   detect_scenes(model, scenes, ...)             OneStageDetector.detect_scenes
@@ -28,6 +30,14 @@ DOTA Task2 (horizontal boxes) is a second merge of the SAME tile rows: with task
 mergebyrec's f64 rows (dafne_scene_merge_hbb_rows_hip: dots4ToRec4 of the Task1 row) and go through py_cpu_nms on the device
 (dafne_hbb_nms_f64_batched_hip, thresh 0.1); every scene dict gains a "task2" entry and write_task2_merged writes what
 mergebyrec writes for the Task2 files task1_to_task2 makes of the tile-level Task1 files.  The detector runs once.
+
+Multi-scale: detect_scenes(scales=(1, 0.5)) splits every scene once per scale -- the tiles of a scale s are the split of the
+scene resampled to scaled_size(h, w, s), cut and resampled from the scene itself in one launch
+(dafne_scene_scaled_tiles_u8_hip: Pillow's 8-bit resize of the whole scene, bicubic by default) -- and all tiles of a scene go
+through ONE merge: the rows of a tile of scale s are divided by s (dafne_scene_merge_rows_scaled_hip: poly2origpoly's
+float(poly + x) / float(rate)), so the results are in the scene's own coordinates.  The pixels of a scaled tile are NOT the
+reference's (its split resizes with cv2.resize(INTER_CUBIC); split_origins(rate != 1) names that split and keeps refusing);
+everything after the pixels is mergebypoly / mergebyrec on tile files named <scene>__<scale>__<left>___<up>.
 
 Scene-level TTA runs the per-image TTA of every tile (modeling/tta.py: DotaDatasetMapperTTA's views, detect_packed without
 post-process, the inverse transforms, one rotated NMS + cap per tile) with views of many tiles batched: per TTA size one
@@ -129,6 +139,85 @@ def gather_tiles(scenes, origins, patch, layout_hwc=None):
     return out
 
 
+RESAMPLE = {"bilinear": _lib.FILTER_BILINEAR, "bicubic": _lib.FILTER_BICUBIC}
+
+
+def scaled_size(h, w, scale):
+    """(new_h, new_w) of an h x w scene resampled by `scale`: max(1, rint(size * scale)), round half to even -- cv2.resize's
+    dsize for dsize=None, saturate_cast<int>(size * fx) [recalled: OpenCV imgproc resize.cpp; cvRound rounds half to even]."""
+    return max(1, int(np.rint(int(h) * float(scale)))), max(1, int(np.rint(int(w) * float(scale))))
+
+
+def _check_scales(scales, resample):
+    """-> the scales as a tuple of floats; ValueError on an empty list, a repeated, non-finite or out-of-range scale, or an
+    unknown filter."""
+    try:
+        scales = tuple(float(s) for s in scales)
+    except TypeError:
+        raise ValueError("scales %r: a sequence of numbers" % (scales,))
+    if not scales:
+        raise ValueError("scales: at least one scale")
+    for s in scales:
+        if not np.isfinite(s) or not 0.0 < s <= 4.0:
+            raise ValueError("scale %r: outside (0, 4]" % (s,))
+    if len(set(scales)) != len(scales):
+        raise ValueError("scales %r: a scale is repeated" % (scales,))
+    if resample not in RESAMPLE:
+        raise ValueError("resample %r: one of %r" % (resample, tuple(sorted(RESAMPLE))))
+    return scales
+
+
+def scale_plan(sizes, scales, patch_size=1024, overlap=200):
+    """The tiles of a multi-scale call, in the order the merge buckets see them: for every scene (sizes: its (h, w)), then
+    every scale in the given order, split_origins of the resampled size in split order.  -> per scene a list of
+    (scale, (new_h, new_w), origins)."""
+    plan = []
+    for h, w in sizes:
+        per = []
+        for s in scales:
+            nh, nw = (int(h), int(w)) if s == 1.0 else scaled_size(h, w, s)
+            per.append((s, (nh, nw), split_origins(nh, nw, patch_size, overlap)))
+        plan.append(per)
+    return plan
+
+
+def gather_scaled_tiles(scenes, scales, origins, patch, resample="bicubic", layout_hwc=None):
+    """scenes: device uint8 images; scales: one scale per scene; origins: per scene a list of (left, up) in the coordinates of
+    the scene resampled to scaled_size(h, w, scale).  -> [T, patch, patch, 3] uint8: tile t is the patch x patch window at its
+    origin of PIL.Image.resize(scene, (new_w, new_h), resample) -- of the whole scene, bit for bit --, zero past the resampled
+    scene's edge.  One launch; the resampled scenes are never written.  (A scene may appear several times, once per scale.)"""
+    L = _lib.load()
+    if resample not in RESAMPLE:
+        raise ValueError("resample %r: one of %r" % (resample, tuple(sorted(RESAMPLE))))
+    descs = []
+    keep = []
+    for img, scale, org in zip(scenes, scales, origins):
+        if not img.is_cuda:
+            raise _lib.DafneHipError("gather_scaled_tiles: the MI355X engine has no CPU path (got a CPU scene)")
+        h, w, hwc = scene_layout(img, layout_hwc)
+        nh, nw = scaled_size(h, w, scale)
+        img = img.contiguous()
+        keep.append(img)
+        for left, up in org:
+            descs.append((img.data_ptr(), h, w, int(hwc), nh, nw, int(left), int(up)))
+    n = len(descs)
+    if n == 0:
+        raise ValueError("gather_scaled_tiles: no tiles")
+    dev = scenes[0].device
+    arr = (_lib.ScaledTile * n)()
+    for k, (p, h, w, hwc, nh, nw, left, up) in enumerate(descs):
+        a = arr[k]
+        a.d_scene, a.h, a.w, a.layout_hwc, a.new_h, a.new_w, a.left, a.up = p, h, w, hwc, nh, nw, left, up
+        a.filter = RESAMPLE[resample]
+    with torch.cuda.device(dev):
+        out = torch.empty((n, patch, patch, 3), dtype=torch.uint8, device=dev)
+        nbytes = L.dafne_scene_scaled_tiles_workspace_bytes(arr, n)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.dafne_scene_scaled_tiles_u8_hip(arr, n, int(patch), _lib.ptr(out), _lib.ptr(ws), nbytes,
+                                                     _lib.current_stream()), "dafne_scene_scaled_tiles_u8_hip")
+    return out
+
+
 def task1_score_mode(cfg):
     """1 where evaluation.task1.task1_scores writes score^2 / centerness (CENTERNESS != none, not CENTERNESS_USE_IN_SCORE)."""
     d = cfg.MODEL.DAFNE
@@ -140,12 +229,14 @@ def skip_mask(cfg):
     return (1 << 15) if bool(cfg.DATASETS.DOTA_REMOVE_CONTAINER_CRANE) else 0
 
 
-def merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, m_cap=None, overflow=None, hbb=False):
+def merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, m_cap=None, overflow=None, hbb=False,
+                    tile_scales=None):
     """rows [T,k_cap,18] f32 + counts [T] (device) + tile_info [T,3] int32 (left, up, scene) -> (dets [B,m_cap,9] f64,
     bucket counts [B] int32, src [B,m_cap] int32, m_cap) with B = n_scenes * n_classes.  m_cap None: sized from the bucket
     counts (a host read of B integers).  overflow: optional device int tensor, read in that same host read; nonzero
     raises (rows the caller truncated).  hbb: the Task2 rows instead, dets [B,m_cap,5] f64 (xmin, ymin, xmax, ymax, score);
-    buckets, counts and src are the same."""
+    buckets, counts and src are the same.  tile_scales: optional [T] split rates (tile_info's left / up are in the resampled
+    scene's coordinates); the rows are (q + left | up) / scale in fp64, i.e. in the scene's own coordinates."""
     L = _lib.load()
     dev = rows.device
     T, k_cap = int(rows.shape[0]), int(rows.shape[1])
@@ -162,11 +253,21 @@ def merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         bcount = torch.empty(nb, dtype=torch.int32, device=dev)
 
-        fn, what = (L.dafne_scene_merge_hbb_rows_hip, "dafne_scene_merge_hbb_rows_hip") if hbb else \
-            (L.dafne_scene_merge_rows_hip, "dafne_scene_merge_rows_hip")
+        if tile_scales is None:
+            fn, what = (L.dafne_scene_merge_hbb_rows_hip, "dafne_scene_merge_hbb_rows_hip") if hbb else \
+                (L.dafne_scene_merge_rows_hip, "dafne_scene_merge_rows_hip")
+            extra = ()
+        else:
+            fn, what = (L.dafne_scene_merge_hbb_rows_scaled_hip, "dafne_scene_merge_hbb_rows_scaled_hip") if hbb else \
+                (L.dafne_scene_merge_rows_scaled_hip, "dafne_scene_merge_rows_scaled_hip")
+            sc = torch.as_tensor(tile_scales, dtype=torch.float64).reshape(-1)
+            if int(sc.numel()) != T or not bool((torch.isfinite(sc) & (sc > 0)).all()):
+                raise ValueError("merge_tile_rows: tile_scales must be %d finite positive numbers" % T)
+            sc = sc.to(dev).contiguous()
+            extra = (_lib.ptr(sc),)
 
         def call(cap, dets, src):
-            _lib.check(fn(_lib.ptr(rows), _lib.ptr(counts), T, k_cap, _lib.ptr(info), int(n_scenes),
+            _lib.check(fn(_lib.ptr(rows), _lib.ptr(counts), T, k_cap, _lib.ptr(info), *extra, int(n_scenes),
                           int(n_classes), int(skip), int(score_mode), int(cap), _lib.ptr(dets),
                           _lib.ptr(bcount), _lib.ptr(src), _lib.ptr(ws), nbytes, _lib.current_stream()), what)
         if m_cap is None:
@@ -249,35 +350,71 @@ def _kept_rows(dets, bcount, src, m_cap, n_scenes, n_classes, k_cap, box_key):
     return out
 
 
-def merge_scenes(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, overflow=None, tasks=("task1",)):
+def merge_scenes(rows, counts, tile_info, n_scenes, n_classes, skip=0, score_mode=0, overflow=None, tasks=("task1",),
+                 tile_scales=None):
     """Tile rows -> per scene {"corners" [K,8] f64, "scores" [K] f64, "labels" [K] int64, "tile" [K], "row" [K]}: class by
     class, each class in the NMS keep order (descending score) -- what mergebypoly writes for that scene.  overflow: see
     merge_tile_rows.  With "task2" in tasks every dict also holds "task2": {"boxes" [K2,4] f64 (xmin, ymin, xmax, ymax),
-    "scores", "labels", "tile", "row"}, what mergebyrec writes for that scene, merged from the same tile rows."""
+    "scores", "labels", "tile", "row"}, what mergebyrec writes for that scene, merged from the same tile rows.  tile_scales:
+    see merge_tile_rows (None: the unscaled entries)."""
     tasks = _check_tasks(tasks)
     k_cap = int(rows.shape[1])
+    kw = {} if tile_scales is None else {"tile_scales": tile_scales}
     dets, bcount, src, m_cap = merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip, score_mode,
-                                               overflow=overflow)
+                                               overflow=overflow, **kw)
     out = _kept_rows(dets, bcount, src, m_cap, n_scenes, n_classes, k_cap, "corners")
     if "task2" in tasks:
         # the same buckets and counts: m_cap is known, no second read
-        dets5, bcount5, src5, _ = merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip, score_mode, m_cap=m_cap, hbb=True)
+        dets5, bcount5, src5, _ = merge_tile_rows(rows, counts, tile_info, n_scenes, n_classes, skip, score_mode, m_cap=m_cap, hbb=True,
+                                                   **kw)
         for r, r2 in zip(out, _kept_rows(dets5, bcount5, src5, m_cap, n_scenes, n_classes, k_cap, "boxes")):
             r["task2"] = r2
     return out
 
 
-def detect_scenes(model, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",)):
+def _detect_tiles(model, tiles, patch, batch):
+    """[T, patch, patch, 3] uint8 tiles -> (rows, counts) of detect_packed(pipelined=True) in batches of `batch`."""
+    from .data.loader import _to_chw_resized, inference_resize_shape
+    cfg = model.cfg
+    nh, nw = inference_resize_shape(cfg, patch, patch)
+    resize = (nh, nw) != (patch, patch)
+    splits = max(1, int(cfg.ENGINE.PIPELINE_SPLITS))
+    T = int(tiles.shape[0])
+    parts = []
+    for b0 in range(0, T, max(1, int(batch))):
+        x = tiles[b0:b0 + batch]
+        n = int(x.shape[0])
+        if resize:
+            # what the test loader does with a patch x patch tile file (data.loader.DAFNeTestMapper.finish): Pillow-exact
+            # resize to the test size, detections scaled back to the tile's own size
+            x = torch.stack([_to_chw_resized(x[i], nh, nw) for i in range(n)])
+            parts.append(model.detect_packed(x, out_hw=[(patch, patch)] * n, pipelined=True, splits=splits))
+        else:
+            parts.append(model.detect_packed(x, layout_hwc=True, pipelined=True, splits=splits))
+    torch.cuda.current_stream().wait_stream(model.side_stream)
+    return torch.cat([r for r, _ in parts]), torch.cat([c for _, c in parts])
+
+
+def detect_scenes(model, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",), scales=(1,),
+                  resample="bicubic"):
     """OneStageDetector.detect_scenes: device uint8 BGR scenes (HWC or CHW) -> one result per scene (merge_scenes' dicts,
     plus "origins": the scene's tile origins in split order; tasks: see merge_scenes).  Tiles of all scenes go through detect_packed(pipelined=True)
-    in batches of `batch` (the engine is batch-invariant: a tile's detections do not depend on its batch)."""
-    from .data.loader import _to_chw_resized, inference_resize_shape
+    in batches of `batch` (the engine is batch-invariant: a tile's detections do not depend on its batch).
+
+    scales: the split rates.  (1,) is the single-scale route.  Otherwise every scene is split once per scale, in the given
+    order (scale_plan): the tiles of scale s are cut from the scene resampled to scaled_size(h, w, s) with Pillow's `resample`
+    filter ("bicubic" / "bilinear"; gather_scaled_tiles; scale 1 is the plain crop), all tiles of a scene are merged in one
+    NMS in the scene's own coordinates, and every result also holds "tile_scales", one per tile, parallel to "origins" (which
+    are in the resampled scene's coordinates)."""
     tasks = _check_tasks(tasks)
+    scales = _check_scales(scales, resample)
     if not scenes:
         return []
     cfg = model.cfg
     dev = model.device
     patch = int(patch_size)
+    if scales != (1.0,):
+        return _detect_scenes_scaled(model, scenes, patch, overlap, batch, layout_hwc, tasks, scales, resample)
     origins = []
     info = []
     for s, img in enumerate(scenes):
@@ -287,28 +424,50 @@ def detect_scenes(model, scenes, patch_size=1024, overlap=200, batch=8, layout_h
         info.extend((left, up, s) for left, up in org)
     with torch.cuda.device(dev):
         tiles = gather_tiles([x.to(dev) for x in scenes], origins, patch, layout_hwc)
-        nh, nw = inference_resize_shape(cfg, patch, patch)
-        resize = (nh, nw) != (patch, patch)
-        splits = max(1, int(cfg.ENGINE.PIPELINE_SPLITS))
-        T = int(tiles.shape[0])
-        parts = []
-        for b0 in range(0, T, max(1, int(batch))):
-            x = tiles[b0:b0 + batch]
-            n = int(x.shape[0])
-            if resize:
-                # what the test loader does with a patch x patch tile file (data.loader.DAFNeTestMapper.finish): Pillow-exact
-                # resize to the test size, detections scaled back to the tile's own size
-                x = torch.stack([_to_chw_resized(x[i], nh, nw) for i in range(n)])
-                parts.append(model.detect_packed(x, out_hw=[(patch, patch)] * n, pipelined=True, splits=splits))
-            else:
-                parts.append(model.detect_packed(x, layout_hwc=True, pipelined=True, splits=splits))
-        torch.cuda.current_stream().wait_stream(model.side_stream)
-        rows = torch.cat([r for r, _ in parts])
-        counts = torch.cat([c for _, c in parts])
+        rows, counts = _detect_tiles(model, tiles, patch, batch)
         res = merge_scenes(rows, counts, info, len(scenes), int(cfg.MODEL.DAFNE.NUM_CLASSES), skip_mask(cfg), task1_score_mode(cfg),
                            tasks=tasks)
     for r, org in zip(res, origins):
         r["origins"] = org
+    return res
+
+
+def _detect_scenes_scaled(model, scenes, patch, overlap, batch, layout_hwc, tasks, scales, resample):
+    cfg = model.cfg
+    dev = model.device
+    plan = scale_plan([scene_layout(img, layout_hwc)[:2] for img in scenes], scales, patch, overlap)
+    info, tile_scales = [], []
+    plain = [[] for _ in scenes]                  # scale 1: origins per scene (gather_tiles)
+    plain_at, scaled_at = [], []                  # positions of the two launches' tiles in the merge order
+    sc_scenes, sc_scales, sc_origins = [], [], []
+    with torch.cuda.device(dev):
+        on_dev = [x.to(dev) for x in scenes]
+        for s, per in enumerate(plan):
+            for scale, _, org in per:
+                at = range(len(info), len(info) + len(org))
+                info.extend((left, up, s) for left, up in org)
+                tile_scales.extend([scale] * len(org))
+                if scale == 1.0:
+                    plain[s] = org
+                    plain_at.extend(at)
+                else:
+                    sc_scenes.append(on_dev[s])
+                    sc_scales.append(scale)
+                    sc_origins.append(org)
+                    scaled_at.extend(at)
+        tiles = torch.empty((len(info), patch, patch, 3), dtype=torch.uint8, device=dev)
+        if plain_at:
+            tiles[torch.as_tensor(plain_at, device=dev)] = gather_tiles(on_dev, plain, patch, layout_hwc)
+        tiles[torch.as_tensor(scaled_at, device=dev)] = gather_scaled_tiles(sc_scenes, sc_scales, sc_origins, patch, resample,
+                                                                            layout_hwc)
+        rows, counts = _detect_tiles(model, tiles, patch, batch)
+        res = merge_scenes(rows, counts, info, len(scenes), int(cfg.MODEL.DAFNE.NUM_CLASSES), skip_mask(cfg), task1_score_mode(cfg),
+                           tasks=tasks, tile_scales=tile_scales)
+    o = 0
+    for r, per in zip(res, plan):
+        r["origins"] = [xy for _, _, org in per for xy in org]
+        r["tile_scales"] = tile_scales[o:o + len(r["origins"])]
+        o += len(r["origins"])
     return res
 
 
@@ -555,10 +714,14 @@ def tta_tile_rows(tta, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc
     return rows, counts, overflow, info, origins
 
 
-def detect_scenes_tta(tta, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",)):
+def detect_scenes_tta(tta, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",), scales=(1,)):
     """OneStageRCNNWithTTA.detect_scenes: device uint8 BGR scenes -> merge_scenes' dicts per scene (plus "origins"); "tile" /
-    "row" index the tiles' merged TTA rows.  The host reads what merge_scenes reads (and the overflow flag with it)."""
+    "row" index the tiles' merged TTA rows.  The host reads what merge_scenes reads (and the overflow flag with it).
+    scales: only (1,) -- the TTA views are cut from the scene itself, not from a resampled scene."""
     tasks = _check_tasks(tasks)
+    if _check_scales(scales, "bicubic") != (1.0,):
+        raise NotImplementedError("scene TTA with scales %r: the TTA views are cut from the scene itself; only scales=(1,) is "
+                                  "built (detect_scenes takes scales)" % (tuple(scales),))
     if not scenes:
         return []
     m = tta.model

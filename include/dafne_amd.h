@@ -648,6 +648,47 @@ size_t dafne_scene_views_workspace_bytes(const dafne_view_src* views, int n_view
 int dafne_scene_views_u8_hip(const dafne_view_src* views, int n_views, int out_h, int out_w, uint8_t* d_out, void* d_ws,
                              size_t ws_bytes, void* stream);
 /*
+ * Tiles of a RESAMPLED scene, cut straight from the original scene (multi-scale whole-scene inference, scene.detect_scenes(
+ * scales=...)): tile t is the patch x patch crop at (left, up) of PIL.Image.resize(scene, (new_w, new_h), filter) -- Pillow's
+ * two-pass 8-bit resampler on the WHOLE scene, so the taps clip at the scene's border and not at the tile's -- and 0 past
+ * new_h / new_w, bit for bit.  filter: DAFNE_FILTER_BILINEAR (triangle, support 1) or DAFNE_FILTER_BICUBIC (a = -0.5, support
+ * 2).  The resampled scene is never written: a workgroup resamples the source rows its output rows need into LDS.
+ *   tiles: HOST array of n_tiles descriptors (checked on the host, copied into d_ws on `stream`); d_scene uint8 [h,w,3]
+ *   (layout_hwc = 1) or [3,h,w] (= 0); new_h, new_w >= 1; 0 <= left < new_w, 0 <= up < new_h.
+ *   d_out_hwc: [n_tiles, patch, patch, 3] uint8, 4-byte aligned (what dafne_scene_tiles_u8_hip writes).
+ * patch % 4 != 0, or a downscale whose filter needs more than 64 taps (bilinear above 31x, bicubic above 15x) ->
+ * DAFNE_E_UNSUPPORTED.  Any number of distinct (size, new size, filter) axes per call.  d_ws:
+ * dafne_scene_scaled_tiles_workspace_bytes(tiles, n_tiles) bytes (descriptors + one coefficient table per distinct axis); 0 =
+ * invalid descriptors.
+ */
+#define DAFNE_FILTER_BILINEAR 0
+#define DAFNE_FILTER_BICUBIC 1
+typedef struct dafne_scaled_tile {
+    const uint8_t* d_scene;
+    int32_t h, w, layout_hwc;
+    int32_t new_h, new_w;
+    int32_t left, up;
+    int32_t filter;
+} dafne_scaled_tile;
+size_t dafne_scene_scaled_tiles_workspace_bytes(const dafne_scaled_tile* tiles, int n_tiles);
+int dafne_scene_scaled_tiles_u8_hip(const dafne_scaled_tile* tiles, int n_tiles, int patch, uint8_t* d_out_hwc, void* d_ws,
+                                    size_t ws_bytes, void* stream);
+/*
+ * dafne_scene_merge_rows_hip / dafne_scene_merge_hbb_rows_hip for tiles of resampled scenes: d_tile_scale [n_tiles] f64
+ * (device), the rate of each tile's split; x_k = (rint(double(v_k) * 100) / 100 + left | up) / scale in fp64, which is
+ * poly2origpoly's float(poly + x) / float(rate) (ResultMerge_multi_process.py), so the rows are in ORIGINAL scene coordinates;
+ * the Task2 row is dots4ToRec4 of those values (min / max after the division).  left / up of d_tile_info are in the resampled
+ * scene's coordinates.  NULL = every scale 1.0: the unscaled entries, bit for bit.  Everything else as the unscaled entries.
+ */
+int dafne_scene_merge_rows_scaled_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap,
+                                      const int32_t* d_tile_info, const double* d_tile_scale, int n_scenes, int n_classes,
+                                      uint64_t skip_mask, int score_mode, int m_cap, double* d_dets, int32_t* d_bucket_counts,
+                                      int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream);
+int dafne_scene_merge_hbb_rows_scaled_hip(const float* d_rows, const int32_t* d_counts, int n_tiles, int k_cap,
+                                          const int32_t* d_tile_info, const double* d_tile_scale, int n_scenes, int n_classes,
+                                          uint64_t skip_mask, int score_mode, int m_cap, double* d_dets5,
+                                          int32_t* d_bucket_counts, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream);
+/*
  * The merge input of OneStageRCNNWithTTA (dafne/modeling/tta.py:237-262) for n_images images on the device: every view's
  * packed rows (detect_packed(do_postprocess=False): d_rows [k_cap, DAFNE_DET_ROW] f32 + *d_count, device pointers per
  * view, so the chunks of several detector calls need no concatenation) back through the inverse of the view's transforms:

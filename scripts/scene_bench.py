@@ -23,6 +23,14 @@ dicts are equal (as run, and with voc_eval's argsort made stable: the synthetic 
 tiles/s recorded in profiles/scene_bench.json).
 
     python scripts/scene_bench.py --score --out profiles/scene_score_bench.json
+
+--scales 1,0.5: multi-scale whole-scene inference.  (a) the pixels: gather_scaled_tiles(resample="bilinear") on every scene at
+0.5 and at 1.5 (one launch) against the two-step device route it replaces for that filter -- dafne_resize_bilinear_u8_hip of
+each whole scene, then gather_tiles on the resized scenes --, alternating --rounds times, device time by events: median, min
+and max of both (bicubic has no two-step route on the device; its launch is timed alone).  (b) detect_scenes(scales=...)
+against detect_packed alone on the same tiles, as in the default mode.
+
+    python scripts/scene_bench.py --scales 1,0.5 --scenes 16 --batch 8 --rounds 5 --warmup 2 --out profiles/scene_scales_bench.json
 """
 import argparse
 import json
@@ -46,6 +54,7 @@ def main():
     ap.add_argument("--tta", action="store_true", help="scene-level TTA against the per-tile TTA route")
     ap.add_argument("--out", default="", help="also write the JSON line to this file")
     ap.add_argument("--views-per-call", type=int, default=0, help="--tta: views per detector call (0: the library's default)")
+    ap.add_argument("--scales", default="", help="multi-scale: comma-separated scales of detect_scenes, e.g. 1,0.5")
     ap.add_argument("--score", action="store_true", help="score_scenes against write_task1_merged + score_task1 on synthetic results")
     ap.add_argument("--score-scenes", type=int, default=400)
     ap.add_argument("--score-dets", type=int, default=200000)
@@ -80,6 +89,9 @@ def main():
     splits = max(1, int(cfg.ENGINE.PIPELINE_SPLITS))
     if args.tta:
         return bench_tta(args, cfg, m, scenes, origins, info, tiles)
+    if args.scales:
+        del tiles
+        return bench_scales(args, cfg, m, scenes)
 
     def tiles_only():
         parts = [m.detect_packed(tiles[b:b + args.batch], layout_hwc=True, pipelined=True, splits=splits)
@@ -135,6 +147,97 @@ def main():
         "tile_rows": int(counts.sum()), "buckets": int(bc.numel()), "m_cap": int(m_cap),
         "merged_detections": int(sum(len(r["scores"]) for r in res)),
         "s_tiles": [round(v, 4) for v in t_tiles], "s_scene": [round(v, 4) for v in t_scene]}))
+
+
+def bench_scales(args, cfg, m, scenes):
+    import torch
+    from dafne_amd import scene as sc
+    from dafne_amd.data.loader import _to_chw_resized
+    scales = tuple(float(v) for v in args.scales.split(","))
+    splits = max(1, int(cfg.ENGINE.PIPELINE_SPLITS))
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def device_ms(f):
+        torch.cuda.synchronize()
+        ev[0].record()
+        out = f()
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]), out
+
+    # (a) the pixels of the scaled splits at 0.5 and 1.5, every scene: the fused launch against resize + gather
+    pix_scales = (0.5, 1.5)
+    pairs = [(img, s) for img in scenes for s in pix_scales]
+    sizes = [sc.scaled_size(args.size, args.size, s) for _, s in pairs]
+    porg = [sc.split_origins(nh, nw) for nh, nw in sizes]
+
+    def fused(resample):
+        return sc.gather_scaled_tiles([p[0] for p in pairs], [p[1] for p in pairs], porg, 1024, resample)
+
+    def two_step():
+        resized = [_to_chw_resized(img, nh, nw) for (img, _), (nh, nw) in zip(pairs, sizes)]
+        return sc.gather_tiles(resized, porg, 1024, layout_hwc=False)
+
+    same = bool(torch.equal(fused("bilinear"), two_step()))
+    ms_fused, ms_two, ms_cubic = [], [], []
+    for _ in range(args.rounds):
+        ms_fused.append(device_ms(lambda: fused("bilinear"))[0])
+        ms_two.append(device_ms(two_step)[0])
+        ms_cubic.append(device_ms(lambda: fused("bicubic"))[0])
+    torch.cuda.empty_cache()
+
+    # (b) detect_scenes(scales=...) against detect_packed alone on the same tiles
+    plan = sc.scale_plan([(args.size, args.size)] * len(scenes), scales)
+    parts = []
+    for img, per in zip(scenes, plan):
+        for s, _, org in per:
+            parts.append(sc.gather_tiles([img], [org], 1024) if s == 1.0 else sc.gather_scaled_tiles([img], [s], [org], 1024))
+    tiles = torch.cat(parts)
+    del parts
+    T = int(tiles.shape[0])
+
+    def tiles_only():
+        out = [m.detect_packed(tiles[b:b + args.batch], layout_hwc=True, pipelined=True, splits=splits) for b in range(0, T, args.batch)]
+        torch.cuda.current_stream().wait_stream(m.side_stream)
+        torch.cuda.synchronize()
+        return out
+
+    def scene_path():
+        r = m.detect_scenes(scenes, batch=args.batch, scales=scales)
+        torch.cuda.synchronize()
+        return r
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        return time.perf_counter() - t0, out
+
+    for _ in range(args.warmup):
+        tiles_only()
+        scene_path()
+    t_tiles, t_scene = [], []
+    for _ in range(args.rounds):
+        t_tiles.append(timed(tiles_only)[0])
+        dt, res = timed(scene_path)
+        t_scene.append(dt)
+    stat = lambda v: {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}      # noqa: E731
+    rate_tiles, rate_scene = T / statistics.median(t_tiles), T / statistics.median(t_scene)
+    line = json.dumps({
+        "mode": "scales", "config": args.config, "scenes": args.scenes, "size": args.size, "scales": list(scales), "batch": args.batch,
+        "rounds": args.rounds, "pixel_scales": list(pix_scales), "pixel_tiles": int(sum(len(o) for o in porg)),
+        "fused_bilinear_ms": stat(ms_fused), "resize_then_gather_bilinear_ms": stat(ms_two), "fused_bicubic_ms": stat(ms_cubic),
+        "fused_over_two_step": round(statistics.median(ms_fused) / statistics.median(ms_two), 3), "fused_equals_two_step": same,
+        "tiles": T, "tiles_per_s_detect_packed": round(rate_tiles, 1), "tiles_per_s_detect_scenes": round(rate_scene, 1),
+        "ratio": round(rate_scene / rate_tiles, 4), "merged_detections": int(sum(len(r["scores"]) for r in res)),
+        "kept_per_scale": {str(s): int(sum(sum(1 for t in r["tile"].cpu().tolist() if ts[t] == s) for r in res))
+                           for ts in [[x for r in res for x in r["tile_scales"]]] for s in scales},
+        "ms_fused": [round(v, 3) for v in ms_fused], "ms_two_step": [round(v, 3) for v in ms_two],
+        "s_tiles": [round(v, 4) for v in t_tiles], "s_scene": [round(v, 4) for v in t_scene]})
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
 
 
 def bench_tta(args, cfg, m, scenes, origins, info, tiles):

@@ -86,6 +86,12 @@ def parse_args(argv=None):
     ap.add_argument("--task2", action="store_true",
                     help="with --scene-dir: also merge the same tile detections as horizontal boxes (DOTA Task2, mergebyrec): writes "
                          "Task2_merged/Task2_<class>.txt, with --zip task2_merged.zip, with --scene-labels results_task2.txt")
+    ap.add_argument("--scene-scales", default="1",
+                    help="with --scene-dir: comma-separated split rates, e.g. 1,0.5 -- every scene is also split after a Pillow "
+                         "resize by each scale (on the device) and all its tiles are merged in one NMS (detect_scenes(scales=...)); "
+                         "not the reference's cv2 split pixels")
+    ap.add_argument("--scene-resample", default="bicubic", choices=("bicubic", "bilinear"),
+                    help="with --scene-scales: the Pillow filter of the scaled splits")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides")
     return ap.parse_args(argv)
 
@@ -118,8 +124,28 @@ def write_synthetic_tiles(root, n, h, w, seed):
             os.path.join(root, "P%04d__1__0___%d.png" % (i // 4, 824 * (i % 4))), compress_level=3)
 
 
+def parse_scene_scales(text):
+    """"1,0.5" -> (1.0, 0.5); ValueError on anything that is not a comma-separated list of numbers."""
+    parts = [p.strip() for p in str(text).split(",")]
+    if not parts or any(not p for p in parts):
+        raise ValueError("--scene-scales %r: a comma-separated list of numbers, e.g. 1,0.5" % (text,))
+    try:
+        return tuple(float(p) for p in parts)
+    except ValueError:
+        raise ValueError("--scene-scales %r: a comma-separated list of numbers, e.g. 1,0.5" % (text,))
+
+
 def scene_args_error(args):
     """The message --scene-dir refuses a combination with, or None."""
+    scales_text = getattr(args, "scene_scales", "1")
+    try:
+        scales = parse_scene_scales(scales_text)
+    except ValueError as e:
+        return str(e)
+    if (scales != (1.0,) or getattr(args, "scene_resample", "bicubic") != "bicubic") and not args.scene_dir:
+        return "--scene-scales / --scene-resample need --scene-dir (they split whole scenes at several rates)"
+    if scales != (1.0,) and args.scene_tta:
+        return "--scene-tta does not support --scene-scales other than 1: the TTA views are cut from the scene itself"
     if args.scene_tta and not args.scene_dir:
         return "--scene-tta needs --scene-dir (it augments the tiles of whole scenes; --tta takes --image-dir)"
     if args.scene_labels and not args.scene_dir:
@@ -185,8 +211,10 @@ def run_scenes(args):
         runner = OneStageRCNNWithTTA(cfg, model)
     else:
         runner = model
+    scales = parse_scene_scales(args.scene_scales)
+    kw = {} if args.scene_tta else {"scales": scales, "resample": args.scene_resample}
     res = runner.detect_scenes(scenes, patch_size=args.patch_size, overlap=args.overlap, batch=args.scene_batch,
-                               tasks=("task1", "task2") if args.task2 else ("task1",))
+                               tasks=("task1", "task2") if args.task2 else ("task1",), **kw)
     names = [r["image_id"] for r in records]
     classnames = (list(de.CLASSNAMES_DOTA_1_0) + ["container-crane"])[:cfg.MODEL.DAFNE.NUM_CLASSES]
     out = args.task1_merged_dir or os.path.join(cfg.OUTPUT_DIR, "scenes")
@@ -197,7 +225,10 @@ def run_scenes(args):
     if args.zip:
         write_zip(out, merged)
     for n, r, s in zip(names, res, scenes):
-        print("scene %s (%dx%d, %d tiles): %d detections" % (n, s.shape[0], s.shape[1], len(r["origins"]), len(r["scores"])))
+        per = ""
+        if "tile_scales" in r:
+            per = ": " + ", ".join("%d at %g" % (r["tile_scales"].count(sc), sc) for sc in scales)
+        print("scene %s (%dx%d, %d tiles%s): %d detections" % (n, s.shape[0], s.shape[1], len(r["origins"]), per, len(r["scores"])))
     print("Task1_merged written to %s" % merged)
     if args.task2:
         merged2 = os.path.join(out, "Task2_merged")
