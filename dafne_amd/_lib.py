@@ -82,6 +82,25 @@ class GnSeg(ctypes.Structure):
     _fields_ = [("d_x", c_void_p), ("H", c_i32), ("W", c_i32), ("tile0", c_i32), ("tiles_per_img", c_i32)]
 
 
+class TargetParams(ctypes.Structure):
+    _fields_ = [("n_images", c_i32), ("n_levels", c_i32), ("n_classes", c_i32), ("flags", c_i32),
+                ("H", c_i32 * 8), ("W", c_i32 * 8), ("stride", c_i32 * 8),
+                ("size_lo", c_float * 8), ("size_hi", c_float * 8), ("radius", c_float * 8)]
+
+
+class LossParams(ctypes.Structure):
+    _fields_ = [("n_images", c_i32), ("n_levels", c_i32), ("n_classes", c_i32), ("flags", c_i32),
+                ("alpha", c_double), ("gamma", c_double), ("beta", c_double), ("ctr_alpha", c_double),
+                ("lambda_cls", c_double), ("lambda_corners", c_double), ("lambda_center", c_double), ("lambda_ctr", c_double)]
+
+
+# dafne_target_params.flags / dafne_loss_params.flags (include/dafne_amd.h)
+TGT_CENTER_SAMPLE, TGT_CENTER_SAMPLE_ONLY, TGT_COMBINE_CENTER_SAMPLE, TGT_IN_BOX_CHECK, TGT_LEVEL_SIZE_FILTERING, \
+    TGT_FPN_STRIDE_NORM = 1, 2, 4, 8, 16, 32
+LOSS_LOGSPACE, LOSS_MODULATION, LOSS_SORT_CORNERS, LOSS_HAS_CENTER_REG, LOSS_COOKED, LOSS_CTR_PLAIN, LOSS_CTR_ORIENTED = \
+    1, 2, 4, 8, 16, 32, 64
+
+
 # name -> (restype, argtypes): every symbol include/dafne_amd.h declares
 SIGNATURES = {
     "dafne_abi_version": (c_int, []),
@@ -185,6 +204,9 @@ SIGNATURES = {
     "dafne_scene_mark_workspace_bytes": (c_size_t, [c_int]),
     "dafne_scene_mark_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_double,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dafne_assign_targets_hip": (c_int, [ctypes.POINTER(TargetParams)] + [c_void_p] * 5 + [c_int] + [c_void_p] * 6),
+    "dafne_losses_workspace_bytes": (c_size_t, [ctypes.POINTER(LossParams), ctypes.POINTER(LevelDesc)]),
+    "dafne_losses_hip": (c_int, [ctypes.POINTER(LossParams), ctypes.POINTER(LevelDesc)] + [c_void_p] * 7 + [c_size_t, c_void_p]),
 }
 
 

@@ -782,6 +782,44 @@ class OneStageDetector(nn.Module):
         ready.synchronize()                      # that batch's post-process (side stream) is done; later batches keep running
         return [{"instances": r} for r in pp.rows_to_instances(rows, counts_h.clone(), out_hw, host_rows=rows_h)]
 
+    # ------------------------------------------------------------ loss values on a labelled batch
+    def validation_losses(self, batched_inputs):
+        """The numbers the reference logs at every training step -- loss/cls, loss/corners, loss/center, loss/ctr
+        (dafne_outputs.py:620-731) -- plus "loss/total", for a labelled batch: list[{"image": uint8 CHW BGR, "instances":
+        Instances with gt_corners / gt_boxes / gt_corners_area / gt_classes at the image's scale}] (the reference's training
+        contract; data.targets.make_gt_instances).  The ordinary eval forward (FrozenBN and GroupNorm: the values of the
+        reference's training forward) on a launch plan of its own, then the assignment and loss kernels on the head's outputs.
+        0-dim fp32 device tensors; nothing is read back to the host.  Forward values only: there is no backward, and forward()
+        keeps raising under self.training."""
+        if self.training:
+            raise NotImplementedError("training is outside the scope of the MI355X inference engine")
+        if self.cfg.ENGINE.WEIGHT_DTYPE == "fp8_e4m3" and self._act_q8 is None and self.cfg.ENGINE.FP8_ACT_CALIBRATION != "off":
+            raise RuntimeError("fp8 model without activation scales: call calibrate_fp8(batch) or set_fp8_act_scales(scales) first")
+        gts = [x["instances"] for x in batched_inputs]
+        batch, valid, _ = self._pack_inputs(batched_inputs)
+        L = _lib.load()
+        n, _, h, w = batch.shape
+        hn, wn = (h + 31) // 32 * 32, (w + 31) // 32 * 32
+        mean = (ctypes.c_float * 3)(*[float(v) for v in self.cfg.MODEL.PIXEL_MEAN])
+        std = (ctypes.c_float * 3)(*[float(v) for v in self.cfg.MODEL.PIXEL_STD])
+        outs = self.proposal_generator.dafne_outputs
+        with torch.cuda.device(batch.device):
+            batch = batch.contiguous()
+            plan = self.plan(n, hn, wn, slot="val")       # its own buffers: a detection call in flight keeps its head outputs
+            vt = None if all(tuple(v) == (h, w) for v in valid) else self._dev_const(valid, torch.int32, (n, 2))
+            _lib.check(L.dafne_preprocess_image_hip(_lib.ptr(batch), 0, n, h, w, _lib.ptr(vt), mean, std, hn, wn,
+                                                    _lib.ptr(plan.stem_in), _lib.current_stream()), "dafne_preprocess_image_hip")
+            plan.run()
+            levels = head_levels(plan.head, self.proposal_generator.fpn_strides)
+            tg = outs.assign_targets([(lv.H, lv.W) for lv in levels], gts, self.device)
+            extras, losses = outs.dafne_losses_packed(levels, tg)
+            total = None
+            for v in losses.values():
+                total = v if total is None else total + v
+            losses["loss/total"] = total
+        self._last_validation = {"plan": plan, "targets": tg, "extras": extras}      # (tests: what the values were computed from)
+        return losses
+
     def inference(self, batched_inputs, detected_instances=None, do_postprocess=True):
         assert not self.training
         return self.forward(batched_inputs, do_postprocess)

@@ -749,6 +749,72 @@ int dafne_scene_mark_hip(const int32_t* d_rank, const double* d_ovmax, const int
                          const int32_t* d_gt_offsets, int n_buckets, const uint8_t* d_difficult, int n_gt, double thresh,
                          uint8_t* d_tp, uint8_t* d_fp, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------- target assignment and loss values (forward values only) */
+/*
+ * dafne_assign_targets_hip: compute_targets_for_locations plus _get_ground_truth's stride division
+ * (dafne/modeling/dafne/dafne_outputs.py:252-503) for a batch.  Ground truth: the boxes of all images packed one after the
+ * other, d_gt_corners [n_gt, 8], d_gt_hbox [n_gt, 4] (x1, y1, x2, y2), d_gt_area [n_gt] f32, d_gt_class [n_gt] int32, and
+ * d_gt_offsets [n_images + 1] int32 ascending from 0 (image i owns rows offsets[i] .. offsets[i + 1]; read on the device and
+ * clamped to [0, n_gt]).  Locations are regenerated as compute_locations (dafne.py:37-44) makes them from H, W, stride.
+ * size_lo / size_hi: the level's size of interest (:183-190); radius: float(stride * POS_RADIUS).
+ * Outputs, LEVEL first, then image, then location (the order of the reference's losses(), :527): position
+ * p = n_images * (locations of the levels before l) + image * H_l * W_l + location;
+ *   d_label [P] int32 (n_classes = background), d_target_ind [P] int32 (row into the packed boxes, -1 for an image without
+ *   boxes), d_reg_corners [P, 8], d_reg_ltrb [P, 4], d_reg_abcd [P, 4] f32 (those of box 0 of the image at background).
+ * fp32 in the reference's operation order: integers equal and floats bit-equal to torch on the CPU for finite inputs.
+ */
+#define DAFNE_TGT_CENTER_SAMPLE 1
+#define DAFNE_TGT_CENTER_SAMPLE_ONLY 2
+#define DAFNE_TGT_COMBINE_CENTER_SAMPLE 4
+#define DAFNE_TGT_IN_BOX_CHECK 8
+#define DAFNE_TGT_LEVEL_SIZE_FILTERING 16
+#define DAFNE_TGT_FPN_STRIDE_NORM 32
+#define DAFNE_TGT_ALL_FLAGS 63
+typedef struct dafne_target_params {
+    int32_t n_images, n_levels, n_classes, flags;      /* n_levels <= 8 */
+    int32_t H[8], W[8], stride[8];
+    float size_lo[8], size_hi[8], radius[8];
+} dafne_target_params;
+int dafne_assign_targets_hip(const dafne_target_params* prm, const float* d_gt_corners, const float* d_gt_hbox,
+                             const float* d_gt_area, const int32_t* d_gt_class, const int32_t* d_gt_offsets, int n_gt,
+                             int32_t* d_label, int32_t* d_target_ind, float* d_reg_corners, float* d_reg_ltrb,
+                             float* d_reg_abcd, void* stream);
+
+/*
+ * dafne_losses_hip: dafne_losses (dafne_outputs.py:620-731) with ModulatedEightPointLoss / SmoothL1Loss
+ * (dafne/modeling/losses/smooth_l1.py) and the sigmoid focal loss  p = sigmoid(x), ce = BCEWithLogits(x, t),
+ * p_t = p t + (1 - p)(1 - t), loss = ce (1 - p_t)^gamma (alpha t + (1 - alpha)(1 - t)), summed.  World size 1.
+ * levels: the head's raw outputs as dafne_decode_levels_hip takes them (corner regression = (center.repeat(4) + delta) *
+ * scale, or delta * scale without d_center, center regression = center * scale, all fp32 as DAFNeHead.forward forms them);
+ * with DAFNE_LOSS_COOKED d_delta is the finished corner regression and d_center the finished center regression.
+ * d_label / d_reg_*: dafne_assign_targets_hip's outputs for the same levels and n_images.
+ * Every term is evaluated in fp64 from these fp32 values -- that is the engine's definition of the loss; the reference's
+ * fp32 result is one rounding of the same formulas.  The centerness target's ratio (min / max)(min / max) is the fp32 value the
+ * reference forms, raised to float(1 / ctr_alpha) in fp64.  Partial sums per workgroup in d_ws, added in index order by a
+ * last workgroup: no floating-point atomics, equal bits from run to run.
+ * d_out6 [6] f64: loss/cls, loss/corners, loss/center, loss/ctr (each times its lambda; 0 for a term the configuration
+ * lacks), num_pos, loss_denorm.  d_ctr_targets [P] f32 or NULL: the centerness target at positives, 0 elsewhere.
+ */
+#define DAFNE_LOSS_LOGSPACE 1
+#define DAFNE_LOSS_MODULATION 2
+#define DAFNE_LOSS_SORT_CORNERS 4
+#define DAFNE_LOSS_HAS_CENTER_REG 8
+#define DAFNE_LOSS_COOKED 16
+#define DAFNE_LOSS_CTR_PLAIN 32
+#define DAFNE_LOSS_CTR_ORIENTED 64
+#define DAFNE_LOSS_ALL_FLAGS 127
+typedef struct dafne_loss_params {
+    int32_t n_images, n_levels, n_classes, flags;
+    double alpha, gamma;        /* focal loss (LOSS_ALPHA, LOSS_GAMMA) */
+    double beta;                /* LOSS_SMOOTH_L1_BETA */
+    double ctr_alpha;           /* CENTERNESS_ALPHA */
+    double lambda_cls, lambda_corners, lambda_center, lambda_ctr;
+} dafne_loss_params;
+size_t dafne_losses_workspace_bytes(const dafne_loss_params* prm, const dafne_level_desc* levels);
+int dafne_losses_hip(const dafne_loss_params* prm, const dafne_level_desc* levels, const int32_t* d_label,
+                     const float* d_reg_corners, const float* d_reg_ltrb, const float* d_reg_abcd, double* d_out6,
+                     float* d_ctr_targets, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,198 @@
+"""Times of the target-assignment and loss kernels at the workload's shape (batch 8, 1024 x 1024, about 100 boxes per image),
+next to a plain torch-on-GPU transcription of the reference's dense formulation (a dozen [K, G] tensors per image, fp32
+losses): profiles/NOTES_targets.md.
+
+    python scripts/targets_bench.py [--batch 8] [--size 1024] [--boxes 100] [--iters 200] [--out FILE]
+
+Device events around `iters` back-to-back calls after a warm-up; the two assignments are compared (labels and indices equal)
+at the timed size before anything is timed.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from dafne_amd import postprocess as pp  # noqa: E402
+from dafne_amd.config import get_cfg  # noqa: E402
+from dafne_amd.data.targets import make_gt_instances  # noqa: E402
+from dafne_amd.modeling.dafne.dafne_outputs import DAFNeOutputs  # noqa: E402
+
+STRIDES = (8, 16, 32, 64, 128)
+INF = 100000000.0
+
+
+def random_boxes(n, rng, size):
+    c = rng.uniform(0, size, (n, 2))
+    long_side = np.exp(rng.uniform(np.log(12.0), np.log(400.0), n))
+    w, h = long_side, long_side / rng.uniform(1, 5, n)
+    a = rng.uniform(0, np.pi, n)
+    ca, sa = np.cos(a), np.sin(a)
+    ux = np.stack([w / 2 * ca - h / 2 * sa, -w / 2 * ca - h / 2 * sa, -w / 2 * ca + h / 2 * sa, w / 2 * ca + h / 2 * sa], 1)
+    uy = np.stack([w / 2 * sa + h / 2 * ca, -w / 2 * sa + h / 2 * ca, -w / 2 * sa - h / 2 * ca, w / 2 * sa - h / 2 * ca], 1)
+    p = np.empty((n, 8))
+    p[:, 0::2], p[:, 1::2] = c[:, :1] + ux, c[:, 1:] + uy
+    return p.astype(np.float32)
+
+
+# ---- the dense formulation in plain torch (what the reference's compute_targets_for_locations / dafne_losses do, op by op)
+def dense_assign(outs, xs, ys, lv, gts):
+    K = xs.shape[0]
+    X, Y = xs[:, None], ys[:, None]
+    rad = torch.tensor([s * outs.radius for s in outs.strides], device=xs.device)[lv][:, None]
+    soi = torch.tensor(outs.sizes_of_interest, dtype=torch.float32, device=xs.device)[lv]
+    res, off = [], 0
+    for g in gts:
+        c, b, area, cls = g
+        G = cls.shape[0]
+        ltrb = torch.stack([X - b[None, :, 0], Y - b[None, :, 1], b[None, :, 2] - X, b[None, :, 3] - Y], 2)
+        abcd = []
+        for e in range(4):
+            n = (e + 1) % 4
+            x1, y1, x2, y2 = c[None, :, 2 * e], c[None, :, 2 * e + 1], c[None, :, 2 * n], c[None, :, 2 * n + 1]
+            abcd.append(torch.abs((y2 - y1) * X - (x2 - x1) * Y + x2 * y1 - y2 * x1) / torch.sqrt((y2 - y1) ** 2 + (x2 - x1) ** 2))
+        abcd = torch.stack(abcd, 2)
+        cor = torch.stack([c[None, :, q] - (X if q % 2 == 0 else Y) for q in range(8)], 2)
+        cx, cy = (b[:, 0] + b[:, 2]) * 0.5, (b[:, 1] + b[:, 3]) * 0.5
+        q0 = torch.maximum(cx[None] - rad, b[None, :, 0])
+        q1 = torch.maximum(cy[None] - rad, b[None, :, 1])
+        q2 = torch.minimum(cx[None] + rad, b[None, :, 2])
+        q3 = torch.minimum(cy[None] + rad, b[None, :, 3])
+        in_cs = torch.stack([X - q0, Y - q1, q2 - X, q3 - Y], -1).min(-1)[0] > 0
+
+        def tri(i, j):
+            ax, ay, bx, by = c[None, :, 2 * i] - X, c[None, :, 2 * i + 1] - Y, c[None, :, 2 * j] - X, c[None, :, 2 * j + 1] - Y
+            return 0.5 * torch.abs(ax * by - ay * bx)
+        in_q = ~((tri(0, 1) + tri(1, 2) + tri(2, 3) + tri(3, 0)) > (area[None] + 1e-3))
+        mx = ltrb.max(2)[0]
+        cared = (mx >= soi[:, [0]]) & (mx <= soi[:, [1]])
+        a = area[None].repeat(K, 1)
+        a[~(in_cs & in_q)] = INF
+        a[~cared] = INF
+        amin, idx = a.min(1)
+        ar = torch.arange(K, device=xs.device)
+        lab = cls[idx].clone()
+        lab[amin == INF] = outs.num_classes
+        sd = torch.tensor(outs.strides, dtype=torch.float32, device=xs.device)[lv][:, None]
+        res.append((lab, idx + off, cor[ar, idx] / sd, ltrb[ar, idx] / sd, abcd[ar, idx] / sd))
+        off += G
+    return res
+
+
+def level_first(per, lv, n_levels):
+    return [torch.cat([torch.cat([p[f][lv == l] for p in per]) for l in range(n_levels)]) for f in range(5)]
+
+
+def dense_losses(outs, logits, corners, center, ctr, tg):
+    lab, _, tc, _, ta = tg
+    C = outs.num_classes
+    pos = torch.nonzero(lab != C).squeeze(1)
+    num_pos = max(pos.numel(), 1.0)
+    t = torch.zeros_like(logits)
+    t[pos, lab[pos]] = 1
+    p = torch.sigmoid(logits)
+    ce = torch.nn.functional.binary_cross_entropy_with_logits(logits, t, reduction="none")
+    pt = p * t + (1 - p) * (1 - t)
+    a = outs.focal_loss_alpha
+    cls = ((a * t + (1 - a) * (1 - t)) * ce * (1 - pt) ** outs.focal_loss_gamma).sum() / num_pos
+    r = ta[pos]
+    lr, tb = r[:, [0, 2]], r[:, [1, 3]]
+    cw = ((lr.min(-1)[0] / lr.max(-1)[0]) * (tb.min(-1)[0] / tb.max(-1)[0])) ** (1 / outs.centerness_alpha)
+    cw[torch.isnan(cw)] = 0
+    denorm = max(float(cw.sum()), 1e-6)          # the reference's .item()
+    beta = outs.loss_beta
+
+    def sl1(x, y):
+        n = torch.abs(x - y)
+        return torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta).log1p()
+    q = pp.sort_quadrilateral(corners[pos])
+    q4 = q.view(-1, 4, 2)
+    l0 = sl1(q, tc[pos]).sum(1)
+    l1 = sl1(q4[:, [1, 2, 3, 0]].reshape(-1, 8), tc[pos]).sum(1)
+    l2 = sl1(q4[:, [3, 0, 1, 2]].reshape(-1, 8), tc[pos]).sum(1)
+    cor = (torch.stack((l0, l1, l2), -1).min(-1)[0] * cw).sum() / denorm
+    cen = (sl1(center[pos], tc[pos].view(-1, 4, 2).mean(1)) * cw[:, None]).sum() / denorm
+    cl = torch.nn.functional.binary_cross_entropy_with_logits(ctr[pos], cw, reduction="sum") / num_pos
+    return torch.stack([cls * outs.lambda_cls, cor * outs.lambda_corners, cen * outs.lambda_center, cl * outs.lambda_ctr])
+
+
+def timed(fn, iters, warmup=10):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3      # microseconds per call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--size", type=int, default=1024)
+    ap.add_argument("--boxes", type=int, default=100)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("targets_bench.py needs an MI355X: a time from a CPU says nothing")
+    dev = torch.device("cuda", 0)
+    cfg = get_cfg()
+    outs = DAFNeOutputs(cfg)
+    rng = np.random.default_rng(0)
+    n, C = args.batch, outs.num_classes
+    shapes = [((args.size + s - 1) // s, (args.size + s - 1) // s) for s in STRIDES]
+    insts = [make_gt_instances(random_boxes(args.boxes, rng, args.size), rng.integers(0, C, args.boxes), (args.size, args.size))
+             for _ in range(n)]
+    for g in insts:                                   # the boxes live on the device, as a training loop would hold them
+        g.gt_corners, g.gt_corners_area, g.gt_classes = g.gt_corners.to(dev), g.gt_corners_area.to(dev), g.gt_classes.to(dev)
+        g.gt_boxes.tensor = g.gt_boxes.tensor.to(dev)
+    levels = []
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for (h, w), s in zip(shapes, STRIDES):
+        rnd = lambda ch, m, sd: torch.randn(n, h, w, ch, device=dev, generator=gen) * sd + m  # noqa: E731
+        levels.append(pp.LevelInput(rnd(C, -3.0, 2.0), rnd(8, 0.0, 1.5), rnd(2, 0.0, 0.5), rnd(1, 0.0, 2.0), s, 1.0))
+    tg = outs.assign_targets(shapes, insts, dev)
+    # the dense formulation on the same inputs
+    from dafne_amd.modeling.dafne.dafne import compute_locations
+    locs = [compute_locations(h, w, s, dev) for (h, w), s in zip(shapes, STRIDES)]
+    xs, ys = torch.cat([l[:, 0] for l in locs]), torch.cat([l[:, 1] for l in locs])
+    lv = torch.cat([torch.full((l.shape[0],), i, device=dev) for i, l in enumerate(locs)])
+    gts = [(g.gt_corners, g.gt_boxes.tensor, g.gt_corners_area, g.gt_classes) for g in insts]
+    dense = level_first(dense_assign(outs, xs, ys, lv, gts), lv, len(shapes))
+    torch.cuda.synchronize()
+    same_labels = bool(torch.equal(dense[0].to(torch.int32), tg.labels))
+    same_inds = bool(torch.equal(dense[1].to(torch.int32), tg.target_inds))
+    flat = lambda k, ch: torch.cat([getattr(l, k).reshape(-1, ch) for l in levels])  # noqa: E731
+    logits, corners, center, ctr = flat("logits", C), flat("delta", 8), flat("center", 2), flat("ctrness", 1)[:, 0]
+    extras, _ = outs.dafne_losses_packed(levels, tg, cooked=True)
+    ref = dense_losses(outs, logits, corners, center, ctr, dense)
+    torch.cuda.synchronize()
+    k64 = extras["values_f64"][:4].cpu().numpy()
+    res = {
+        "shape": {"batch": n, "size": args.size, "boxes_per_image": args.boxes, "locations_per_image": int(xs.shape[0]),
+                  "positives": float(extras["values_f64"][4])},
+        "labels_equal": same_labels, "target_inds_equal": same_inds,
+        "loss_kernel_fp64": k64.tolist(), "loss_dense_fp32": ref.cpu().tolist(),
+        "assign_call_us": timed(lambda: outs.assign_targets(shapes, insts, dev), args.iters),
+        "loss_call_us": timed(lambda: outs.dafne_losses_packed(levels, tg, cooked=True), args.iters),
+        "assign_dense_torch_us": timed(lambda: dense_assign(outs, xs, ys, lv, gts), max(5, args.iters // 20), warmup=3),
+        "loss_dense_torch_us": timed(lambda: dense_losses(outs, logits, corners, center, ctr, dense), max(5, args.iters // 4), warmup=3),
+        "iters": args.iters,
+    }
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -92,6 +92,10 @@ def parse_args(argv=None):
                          "not the reference's cv2 split pixels")
     ap.add_argument("--scene-resample", default="bicubic", choices=("bicubic", "bilinear"),
                     help="with --scene-scales: the Pillow filter of the scaled splits")
+    ap.add_argument("--val-loss", action="store_true",
+                    help="with --image-dir and --label-dir: the loss values the reference logs while training (loss/cls, loss/corners, "
+                         "loss/center, loss/ctr) on a labelled split, one JSON line (OneStageDetector.validation_losses)")
+    ap.add_argument("--label-dir", default="", help="with --val-loss: DOTA-format labelTxt files, <image stem>.txt per image")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides")
     return ap.parse_args(argv)
 
@@ -249,6 +253,64 @@ def run_scenes(args):
                 print(f"{k: <18}: {v:2.4f}")
             print("results_task2.txt written to %s" % out)
     return res
+
+
+def run_val_loss(args):
+    """--val-loss --image-dir DIR --label-dir DIR: every image goes through the test loader (its resize), its labelTxt boxes are
+    scaled by the same ratio, and OneStageDetector.validation_losses runs on batches of --batch images.  Prints the
+    batch-size-weighted mean of each term as one JSON line; the per-batch values stay on the device until the end."""
+    import json
+    import dafne_amd.modeling  # noqa: F401
+    from dafne_amd.checkpoint import load_weights
+    from dafne_amd.config import load_cfg
+    from dafne_amd.data import DAFNeTestMapper, list_image_records
+    from dafne_amd.data.targets import gt_instances_from_objects
+    from dafne_amd.evaluation import dota_evaluation as de
+    from dafne_amd.registry import build_model
+
+    if not args.image_dir or not args.label_dir:
+        raise SystemExit("--val-loss needs --image-dir and --label-dir")
+    cfg = load_cfg(args.config_file, args.opts)
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_net.py needs an MI355X: the HIP path has no CPU fallback")
+    dev = torch.device("cuda", 0)
+    model = build_model(cfg)
+    if args.weights or cfg.MODEL.WEIGHTS:
+        missing, unexpected = load_weights(model, args.weights or cfg.MODEL.WEIGHTS)
+        print("loaded weights: %d missing, %d unexpected keys" % (len(missing), len(unexpected)))
+    else:
+        import bench
+        model.load_state_dict(bench.seeded_state_dict(model, args.seed))
+    model.to(dev)
+    model.invalidate()
+    records = list_image_records(args.image_dir)
+    if args.num_images > 0:
+        records = records[:args.num_images]
+    if not records:
+        raise SystemExit("--image-dir %s holds no image files" % args.image_dir)
+    classnames = (list(de.CLASSNAMES_DOTA_1_0) + ["container-crane"])[:cfg.MODEL.DAFNE.NUM_CLASSES]      # the scene route's list
+    mapper = DAFNeTestMapper(cfg, dev)
+    sort = bool(cfg.MODEL.DAFNE.SORT_CORNERS_DATALOADER)
+    sums, seen = None, 0
+    for b0 in range(0, len(records), max(1, args.batch)):
+        inputs = []
+        for r in records[b0:b0 + max(1, args.batch)]:
+            x = mapper(r)
+            nh, nw = int(x["image"].shape[1]), int(x["image"].shape[2])
+            path = os.path.join(args.label_dir, "%s.txt" % r["image_id"])
+            objs = de.parse_gt(path) if os.path.exists(path) else []
+            x["instances"] = gt_instances_from_objects(objs, classnames, (nh, nw), ratio=(nw / x["width"], nh / x["height"]), sort=sort)
+            inputs.append(x)
+        vals = model.validation_losses(inputs)
+        keys = sorted(vals)
+        row = torch.stack([vals[k].double() for k in keys]) * len(inputs)
+        sums = row if sums is None else sums + row
+        seen += len(inputs)
+    mean = (sums / seen).cpu().tolist()
+    out = {k: v for k, v in zip(keys, mean)}
+    out["images"] = seen
+    print(json.dumps(out))
+    return out
 
 
 def run(args, rank=0, world=1, local_rank=0):
@@ -453,6 +515,8 @@ def main(argv=None):
         raise SystemExit("eval_net.py: " + err)
     if args.scene_dir:
         return run_scenes(args)
+    if args.val_loss:
+        return run_val_loss(args)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:            # under torch.distributed.run
         return _distributed_main(args)
     if args.num_gpus > 1:                                      # plain_train_net.py:660-671: launch one process per GPU
