@@ -11,11 +11,11 @@ dafne/modeling/backbone/fpn.py:16-37,58-91 and dafne/modeling/dafne/dafne.py:
 350-494 (center-to-corner branch).
 """
 import ctypes
-import os
 
 import torch
 
 from . import _lib
+from .engine_options import EngineOptions
 
 BF16 = torch.bfloat16
 STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3)}
@@ -268,15 +268,22 @@ def pack_conv3x3_frag16(w):
     return w.reshape(cout // 256, 8, 2, 16, 72, 4, 8).permute(0, 1, 4, 2, 5, 3, 6).contiguous().reshape(-1)   # nt, w, m, cb, q, r, e
 
 
-def rp_frag16():
-    """The resident-patch kernel's matrix instruction: v_mfma_f32_16x16x32_bf16 (default; 6-8 % fewer joules per flop on this package)
-    or, DAFNE_RP_MFMA16=0, v_mfma_f32_32x32x16_bf16 (bit-identical to the generic kernels; A/B runs and the parity tests of that form)."""
-    return os.environ.get("DAFNE_RP_MFMA16", "1") != "0"
+def pack_rp(w, options=None):
+    """(fragment-major weights, flag bits) of a resident-patch call in the form options.rp_mfma16 selects: v_mfma_f32_16x16x32_bf16
+    (default; 6-8 % fewer joules per flop on this package) or v_mfma_f32_32x32x16_bf16 (bit-identical to the generic kernels; A/B
+    runs and the parity tests of that form).  The plans pass P["options"]; without options: the form a model packed now would use."""
+    options = options or EngineOptions.from_env()
+    return (pack_conv3x3_frag16(w), F_FRAG16) if options.rp_mfma16 else (pack_conv3x3_frag(w), 0)
 
 
-def pack_rp(w):
-    """(fragment-major weights, flag bits) of a resident-patch call in the form rp_frag16() selects."""
-    return (pack_conv3x3_frag16(w), F_FRAG16) if rp_frag16() else (pack_conv3x3_frag(w), 0)
+def rp_weights(P, key, wgt):
+    """The resident-patch weights of P[key], packed on first use in the ONE form P["options"] dictates -> (wfrag, frag16)."""
+    f16 = P["options"].rp_mfma16
+    fkey, other = (key + ".frag16", key + ".frag") if f16 else (key + ".frag", key + ".frag16")
+    assert other not in P, "one resident-patch form per model: %s" % other
+    if fkey not in P:
+        P[fkey] = pack_rp(wgt, P["options"])[0]
+    return P[fkey], f16
 
 
 def pack_conv_frag(w):
@@ -300,12 +307,6 @@ def rp_scratch(device):
     if key not in _RP_SCRATCH:
         _RP_SCRATCH[key] = torch.empty(_lib.load().dafne_conv3x3_c256_scratch_bytes(), dtype=torch.uint8, device=device)
     return _RP_SCRATCH[key]
-
-
-def use_rp_kernel():
-    """conv3x3_rp_kernel (resident patch, weights streamed to registers) for the 256-channel 3x3 layers; DAFNE_CONV_RP=0
-    keeps them on conv3x3_patch_kernel (A/B runs)."""
-    return os.environ.get("DAFNE_CONV_RP", "1") != "0"
 
 
 def pack_b2b_narrow(w3, w1, wsc=None):
@@ -392,7 +393,8 @@ class ConvCall:
         tile of every image finalises the GroupNorm statistics of the OUTPUT (no dafne_groupnorm_finalize_hip launch).
         wfrag: fragment-major bf16 weights (pack_conv3x3_frag; frag16: pack_conv3x3_frag16, flag F_FRAG16) -> the call goes to dafne_conv3x3_c256_hip (resident-patch
         kernel: 3x3 s1 p1, Cin 256, Cout % 256 == 0; its own tile geometry).
-        shared_gpu: the plan this call belongs to runs next to other plans on concurrent streams (no F_EXCL hint)."""
+        shared_gpu: the plan this call belongs to runs next to other plans on concurrent streams: no F_EXCL hint (the plan
+        builders pass False there when P["options"].shared_excl asks for the hint all the same)."""
         L = _lib.load()
         self.fp8 = fp8
         self.wfrag = wfrag
@@ -403,7 +405,7 @@ class ConvCall:
         self.keep = (w, b, gn_partial, [s for s in segs], gn_in, fp8, gn_fin, wfrag)
         gi = [t.data_ptr() for t in gn_in] if gn_in is not None else [None, None, None]
         gf = (gn_fin[0].data_ptr(), gn_fin[1].data_ptr(), float(gn_fin[2])) if gn_fin is not None else (None, None, 0.0)
-        if not shared_gpu or os.environ.get("DAFNE_SHARED_EXCL", "0") == "1":
+        if not shared_gpu:
             flags |= F_EXCL             # hint (results unchanged): the plan this call belongs to has the GPU to itself
         self.prm = _lib.ConvParams(n_images, len(segs), cin, cout, k, k, stride, pad, flags,
                                    w.data_ptr(), b.data_ptr() if b is not None else None,
@@ -503,13 +505,8 @@ class ConvPairCall:
             _lib.check(rc, "dafne_conv3x3_c256_pair_hip")
 
 
-def use_wr_kernel():
-    """conv_wr_kernel (128 px x 256 ch tiles, weights -> registers, deterministic split-K) for the small-M layers it takes
-    (res5, FPN laterals / P4-P5 outputs / P6 / P7, the stride-2 projections); DAFNE_CONV_WR=0 keeps them on conv_igemm /
-    conv_stream (A/B runs)."""
-    return os.environ.get("DAFNE_CONV_WR", "1") != "0"
-
-
+# conv_wr_kernel (128 px x 256 ch tiles, weights -> registers, deterministic split-K) takes the small-M layers wr_takes names
+# (res5, FPN laterals / P4-P5 outputs / P6 / P7, the stride-2 projections) unless P["options"].conv_wr is off (A/B runs)
 WR_NOMINAL_BATCH = 8      # conv_wr.hip kNominalBatch: the choice below and the kernel's slice count look at 8 images' worth of pixels,
 
 
@@ -616,16 +613,18 @@ class DensePlan:
         pool = Pool(device)
         self.pool = pool
 
+        opt = P["options"]          # (EngineOptions, fixed when the weights were packed: every plan of a model follows it)
+        shared = self.shared_gpu and not opt.shared_excl        # this plan's launches carry no F_EXCL hint
         act_q8 = P.get("act_q8") or {}
-        wr_on = use_wr_kernel()
+        wr_on = opt.conv_wr
         self.wr_ws = WrWorkspace(device)
         # conv3x3_c64.hip: 65 -> 49 us per launch when it has the GPU to itself, but nothing in the timed 3-stream layout (its
         # persistent workgroups hold every CU's LDS, so the other sub-batches' kernels cannot share the chip with it): opt-in
-        use_c64 = os.environ.get("DAFNE_CONV_C64", "0") == "1"
+        use_c64 = opt.conv_c64
         # whole-block kernels write Y = relu(conv3(T) + X) OVER X when X is dead after the block (an identity block's input, or
         # block 0's projection output): a tile reads its own X rows and nobody else's (the halo is on the 3x3's input only), so
         # the stores go to DRAM pages the same workgroup has just read (open rows, lines still in L2)
-        inplace_res = os.environ.get("DAFNE_INPLACE_RES", "1") != "0"
+        inplace_res = opt.inplace_res
 
         def res_dead(sc_, x_, b_):
             # the shortcut operand is not needed after the block: block 0's projection output always; an identity block's input
@@ -661,7 +660,7 @@ class DensePlan:
                     fp8 = (q8[1] / act_q8[key], act_q8[key])       # oscale = weight scale / in_qscale
             c = ConvCall(q8[0] if fp8 else wgt, bias, cin, cout, k, stride, pad, flags,
                          [(tin.t, o.t, res.t if res is not None else None, tin.h, tin.w, ho, wo)], n, fp8=fp8,
-                         shared_gpu=self.shared_gpu)
+                         shared_gpu=shared)
             if (fp8 is None and wr_on and wr_takes(k, stride, cin, cout, WR_NOMINAL_BATCH * ho * wo) and bias is not None
                     and L.dafne_conv2d_wr_ok(ctypes.byref(c.prm), c.segs)):
                 # small-M layer (res5, FPN top): 128 px x 256 ch tiles, weights -> registers, split-K
@@ -672,14 +671,11 @@ class DensePlan:
                 self.flops += w.flops
                 return o
             assert not (flags & F_RELU_INPUT), "only conv_wr rectifies its input on load (the caller checks wr_takes)"
-            if fp8 is None and k == 3 and cin == 256 and use_rp_kernel() and c.kernel_id() == 6 and c.rp_ok():
+            if fp8 is None and k == 3 and cin == 256 and opt.conv_rp and c.kernel_id() == 6 and c.rp_ok():
                 # 256-channel 3x3 layers the patch kernel would take (FPN outputs): resident-patch kernel
-                f16 = rp_frag16()
-                fkey = key + (".frag16" if f16 else ".frag")
-                if fkey not in P:
-                    P[fkey] = pack_rp(wgt)[0]
+                wfrag, f16 = rp_weights(P, key, wgt)
                 c = ConvCall(wgt, bias, cin, cout, k, stride, pad, flags,
-                             [(tin.t, o.t, None, tin.h, tin.w, ho, wo)], n, wfrag=P[fkey], shared_gpu=self.shared_gpu, frag16=f16)
+                             [(tin.t, o.t, None, tin.h, tin.w, ho, wo)], n, wfrag=wfrag, shared_gpu=shared, frag16=f16)
             self.calls.append(c)
             self.flops += c.flops
             return o
@@ -690,10 +686,10 @@ class DensePlan:
         x = pool.get(n, h // 4, w // 4, 64)
         stem_flops = 2 * n * (h // 2) * (w // 2) * 64 * 7 * 7 * 3
         stem_y1 = None            # res2.0's conv1 output when the stem kernel computed it
-        if os.environ.get("DAFNE_FUSE_STEM", "1") != "0":
+        if opt.fuse_stem:
             # conv7x7/s2 + ReLU + max-pool in one kernel: the half-resolution map never reaches HBM
             c1 = P.get("res2.0.conv1")
-            if (os.environ.get("DAFNE_FUSE_STEM_CONV1", "1") != "0" and c1 is not None and tuple(c1[0].shape) == (64, 64)
+            if (opt.fuse_stem_conv1 and c1 is not None and tuple(c1[0].shape) == (64, 64)
                     and c1[1] is not None):
                 # ... and res2.0's first convolution (1x1, 64 -> 64, ReLU) on the pooled tile while it is in LDS
                 # (stem_pool.hip CONV1): the pooled map is not read back by a launch of its own (67 MB at batch 8)
@@ -714,7 +710,7 @@ class DensePlan:
         else:
             stem_out = pool.get(n, h // 2, w // 2, 64)
             c = ConvCall(wgt, bias, 4, 64, 7, 2, 3, F_RELU,
-                         [(self.stem_in, stem_out.t, None, h + 6, w + 6, h // 2, w // 2)], n, shared_gpu=self.shared_gpu)
+                         [(self.stem_in, stem_out.t, None, h + 6, w + 6, h // 2, w // 2)], n, shared_gpu=shared)
             self.calls.append(c)
             self.flops += c.flops
             self.calls.append(FnCall(L.dafne_maxpool3x3s2_nhwc_bf16_hip,
@@ -723,18 +719,14 @@ class DensePlan:
             pool.put(stem_out)
 
         feats = {}
-        fuse_b2b = os.environ.get("DAFNE_FUSE_B2B", "1") != "0"
-        fuse_narrow = fuse_b2b and os.environ.get("DAFNE_FUSE_B2B_NARROW", "1") != "0"
-        fuse_mid = fuse_b2b and os.environ.get("DAFNE_FUSE_B2B_MID", "1") != "0"
-        fuse_bneck = fuse_b2b and os.environ.get("DAFNE_FUSE_BNECK", "1") != "0"
+        fuse_b2b, fuse_narrow, fuse_mid, fuse_bneck = opt.fuse_b2b, opt.b2b_narrow_on, opt.b2b_mid_on, opt.bneck_on
         bneck_scratch = None
         blk_scratch = None
         blk_mid_scratch = None
-        fuse_blk_mid = fuse_mid and os.environ.get("DAFNE_FUSE_BLK_MID", "1") != "0"
-        fuse_blk_narrow = fuse_narrow and os.environ.get("DAFNE_FUSE_BLK_NARROW", "1") != "0"
+        fuse_blk_mid, fuse_blk_narrow = opt.blk_mid_on, opt.blk_narrow_on
         # the last block of a stage nobody but the next stage reads is computed only at the pixels the next stage's stride-2
-        # 1x1 layers touch (conv_blk_narrow_s2.hip); DAFNE_RES2_TAIL_S2=0: the full map (A/B runs)
-        tail_s2 = os.environ.get("DAFNE_RES2_TAIL_S2", "1") != "0"
+        # 1x1 layers touch (conv_blk_narrow_s2.hip); off: the full map (A/B runs)
+        tail_s2 = opt.res2_tail_s2
         blk_s2_scratch = None
         x_compact = False         # x holds only the even pixels of the stage output: the next block 0 reads it with stride 1
         for si, nb in enumerate(STAGE_BLOCKS[depth]):
@@ -762,7 +754,7 @@ class DensePlan:
                 q8_2 = P.get(p + "conv2.fp8")
                 bn_head = b + 1 < nb                  # the stage's last block has no next conv1: the kernel's no-head form
                 body_fused = (fuse_bneck and tuple(w3.shape) == (1024, 256) and (not bn_head or tuple(P[nxt][0].shape) == (256, 1024))
-                              and (bn_head or os.environ.get("DAFNE_FUSE_BNECK_LAST", "1") != "0")
+                              and (bn_head or opt.fuse_bneck_last)
                               and tuple(w2.shape) == (256, 2304) and y1.c == 256
                               # an fp8 model's conv2 takes e4m3 activations on the fp8 MFMA kernel (its definition): not fused
                               and not (q8_2 is not None and (calib is not None or (p + "conv2") in act_q8)))
@@ -961,10 +953,10 @@ class DensePlan:
             prev = lat
         p6 = conv("p6", outs["p5"], 3, 2, 1, 0)
         # P7 = conv(relu(P6)), P6 itself stays un-rectified as a head input: conv_wr rectifies its pixel operand on load
-        # (F_RELU_INPUT); DAFNE_P7_RELU_IN=0, or a P7 that conv_wr does not take: a rectified copy of P6 (relu_copy)
+        # (F_RELU_INPUT); p7_relu_in off, or a P7 that conv_wr does not take: a rectified copy of P6 (relu_copy)
         w7, b7 = P["p7"]
         ho7, wo7 = conv_out_hw(p6.h, p6.w, 3, 2, 1)
-        if (os.environ.get("DAFNE_P7_RELU_IN", "1") != "0" and wr_on and b7 is not None
+        if (opt.p7_relu_in and wr_on and b7 is not None
                 and wr_takes(3, 2, p6.c, w7.shape[0], WR_NOMINAL_BATCH * ho7 * wo7)):
             p7 = conv("p7", p6, 3, 2, 1, F_RELU_INPUT)
         else:
@@ -1092,17 +1084,17 @@ class HeadPlan:
         # the tower paired with cls_tower.i in one launch: the other FPN-fed tower
         partner = "center_tower" if stacked else "corners_tower"
         calls = plan.calls
-        sg = bool(getattr(plan, "shared_gpu", False))
-        fuse_gn = os.environ.get("DAFNE_FUSE_GN", "1") != "0"
-        fuse_gnfin = os.environ.get("DAFNE_FUSE_GNFIN", "1") != "0"
+        opt = P["options"]
+        shared_gpu = bool(getattr(plan, "shared_gpu", False))
+        sg = shared_gpu and not opt.shared_excl          # the launches carry no F_EXCL hint
+        fuse_gn, fuse_gnfin = opt.fuse_gn, opt.fuse_gnfin
 
         def seg_list(ins, outs, f32=False):
             return [(i.t, (o if f32 else o.t), None, i.h, i.w, i.h, i.w) for i, o in zip(ins, outs)]
 
         # (round 5: pairs in the sub-batch plans of the pipelined step as well -- with three sub-batches of unequal size 1371-1373
         # against 1356-1365 img/s, two alternating runs; in round 3's in-phase layout the pairs cost 1-4 % there)
-        pair_towers = os.environ.get("DAFNE_RP_PAIR", "1") != "0" and (not getattr(plan, "shared_gpu", False)
-                                                                       or os.environ.get("DAFNE_RP_PAIR_SHARED", "1") == "1")
+        pair_towers = opt.pair_towers(shared_gpu)
         deferred = []              # intermediate maps of the paired towers: released when BOTH towers are built (see below)
 
         def tower(name, ins, in_gn, consumers):
@@ -1129,24 +1121,20 @@ class HeadPlan:
                 # M-tile geometry comes from the library (the kernel choice fixes the tile shape; the fp8 kernel always
                 # uses the patch kernel's tiles, the bf16 one only when the launch has enough of them)
                 probe = ConvCall(wgt, bias, C, C, 3, 1, 1, flags & ~F_GN, seg_list(cur, outs), n, gn_in=cur_gn, shared_gpu=sg)
-                rp_on = use_rp_kernel() and C == 256
+                rp_on = opt.conv_rp and C == 256
                 if probe.kernel_id() < 0 and not (rp_on and probe.rp_ok()):
                     probe.kernel_name()            # refused (e.g. a batch beyond 32-bit offsets): raise the library's message
                                                    # here, not a tile count of -1 further down
                 use_fp8 = q8 is not None and aq is not None and (cur_gn is None or probe.kernel_id() == 6 or (rp_on and probe.rp_ok()))
                 # (the FPN-fed layer 0 of a SMALL plan -- the 2-image sub-batch of the timed layout -- takes the generic tile, kernel
                 # id != 6, and is then followed by ONE dafne_groupnorm_finalize_hip launch per tower: the two gn_finalize launches
-                # per step in the pipelined rocprof stats.  DAFNE_RP_LAYER0=1 puts it on the persistent kernel with fused finalize:
+                # per step in the pipelined rocprof stats.  rp_layer0 puts it on the persistent kernel with fused finalize:
                 # measured -0.3 .. 0 % in the timed layout (round 4), so it stays opt-in)
-                rp_small = os.environ.get("DAFNE_RP_LAYER0", "0") == "1"
+                rp_small = opt.rp_layer0
                 use_rp = rp_on and not use_fp8 and probe.rp_ok() and (cur_gn is not None or probe.kernel_id() == 6 or rp_small)
-                wfrag = None
-                f16 = use_rp and rp_frag16()
+                wfrag, f16 = None, False
                 if use_rp:
-                    fkey = lkey + (".frag16" if f16 else ".frag")
-                    if fkey not in P:
-                        P[fkey] = pack_rp(wgt)[0]
-                    wfrag = P[fkey]
+                    wfrag, f16 = rp_weights(P, lkey, wgt)
                     probe = ConvCall(wgt, bias, C, C, 3, 1, 1, flags & ~F_GN, seg_list(cur, outs), n, gn_in=cur_gn, wfrag=wfrag, shared_gpu=sg,
                                      frag16=f16)
                 if use_fp8:
@@ -1210,7 +1198,7 @@ class HeadPlan:
                 cur, cur_gn = outs, nxt_gn
             return cur, cur_gn
 
-        fuse_pred = os.environ.get("DAFNE_FUSE_GN_PRED", "1") != "0"
+        fuse_pred = opt.fuse_gn_pred
         cls_t, cls_gn = tower("cls_tower", feats, None, [("cls_logits", num_classes, F_F32)] if fuse_pred else [])
         if stacked:
             ctr_t, ctr_gn = tower("center_tower", feats, None,
@@ -1274,11 +1262,12 @@ def _wq(w, fp8):
     return quantize_weight_e4m3(w)[2] if fp8 else w
 
 
-def pack_backbone_weights(sd, depth, device, prefix="backbone.", fp8=False):
+def pack_backbone_weights(sd, depth, device, prefix="backbone.", fp8=False, options=None):
     """state dict with the reference checkpoint's names -> packed
     backbone weights; FrozenBN folded into weight scale + bias.  fp8: the folded weights are quantised to e4m3 with
-    power-of-two per-channel scales (quantize_weight_e4m3) and run, exactly dequantised, on the bf16 kernels."""
-    P = {}
+    power-of-two per-channel scales (quantize_weight_e4m3) and run, exactly dequantised, on the bf16 kernels.
+    options: the EngineOptions every plan built from these weights follows (P["options"]); None: EngineOptions.from_env(), read now."""
+    P = {"options": options or EngineOptions.from_env()}
     bu = prefix + "bottom_up."
 
     def cb(k):
@@ -1310,7 +1299,7 @@ def pack_backbone_weights(sd, depth, device, prefix="backbone.", fp8=False):
     return P
 
 
-def pack_head_weights(sd, device, prefix="proposal_generator.dafne_head.", fp8=False):
+def pack_head_weights(sd, device, prefix="proposal_generator.dafne_head.", fp8=False, options=None):
     """DAFNeHead parameters -> packed weights.  corners_pred and ctrness both read
     the corners tower (dafne.py:403,467-468) and are fused into one 9-channel conv (8 without centerness).
     Offset head: base_corners is folded into corners_pred's bias, so the base is added before the Scale as in the
@@ -1320,8 +1309,9 @@ def pack_head_weights(sd, device, prefix="proposal_generator.dafne_head.", fp8=F
     tower part (the first C input channels), which joins the fused prediction conv as channels 2k, 2k+1, and the
     chain part, which goes to dafne_corner_chain_hip (P["corner_chain"], 216 fp32 weights).
     fp8: every weight is the dequantised e4m3 weight; the tower layers additionally get key + ".fp8" =
-    (e4m3 bytes, scale) for the fp8 MFMA kernel (HeadPlan uses it where the input is normalised on load)."""
-    P = {}
+    (e4m3 bytes, scale) for the fp8 MFMA kernel (HeadPlan uses it where the input is normalised on load).
+    options: as in pack_backbone_weights."""
+    P = {"options": options or EngineOptions.from_env()}
     hp = prefix
     mode = head_mode_of(sd, prefix)
     strategy, has_ctr = mode
@@ -1366,13 +1356,16 @@ def pack_head_weights(sd, device, prefix="proposal_generator.dafne_head.", fp8=F
 
 def pack_model_weights(sd, depth, device, weight_dtype="bf16", fp8_kernel="patch"):
     """weight_dtype: "bf16" or "fp8_e4m3" (cfg.ENGINE.WEIGHT_DTYPE; BASELINE config 5); fp8_kernel: cfg.ENGINE.FP8_CONV3X3_KERNEL
-    (FP8_KERNELS: "patch" only since round 6; kept in the packed weights because a kernel's rounding is part of the model)."""
+    (FP8_KERNELS: "patch" only since round 6; kept in the packed weights because a kernel's rounding is part of the model).
+    For the same reason the engine switches (EngineOptions; table in INTEGRATION.md, "Engine switches") are resolved
+    HERE, once (EngineOptions.from_env()), and kept as P["options"]: the plans never look anywhere else."""
     if weight_dtype not in ("bf16", "fp8_e4m3"):
         raise NotImplementedError("ENGINE.WEIGHT_DTYPE %r (bf16 or fp8_e4m3)" % (weight_dtype,))
     if fp8_kernel not in FP8_KERNELS:
         raise NotImplementedError("ENGINE.FP8_CONV3X3_KERNEL %r (%s)" % (fp8_kernel, " or ".join(FP8_KERNELS)))
     fp8 = weight_dtype == "fp8_e4m3"
-    P = pack_backbone_weights(sd, depth, device, fp8=fp8)
-    P.update(pack_head_weights(sd, device, fp8=fp8))
+    options = EngineOptions.from_env()
+    P = pack_backbone_weights(sd, depth, device, fp8=fp8, options=options)
+    P.update(pack_head_weights(sd, device, fp8=fp8, options=options))
     P["fp8_kernel"] = fp8_kernel
     return P

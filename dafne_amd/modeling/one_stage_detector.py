@@ -173,7 +173,7 @@ class OneStageDetector(nn.Module):
         want = set(k[:-4] for k in P if k.endswith(".fp8") and not k.endswith(".frag")
                    and (k.startswith("res") or k.startswith("fpn_output") or k in ("cls_tower.0.fp8", "center_tower.0.fp8")))
         # ... plus whatever else a calibration plan of this build probes (corners_tower.0 when the center tower's GroupNorm is
-        # not fused into it: DAFNE_FUSE_GN=0 / a kernel-selection fallback): any layer with e4m3 weights may carry a scale,
+        # not fused into it: EngineOptions.fuse_gn off / a kernel-selection fallback): any layer with e4m3 weights may carry a scale,
         # the plain-input ones above must
         allowed = set(k[:-4] for k in P if k.endswith(".fp8") and not k.endswith(".frag"))
         if not (want <= set(scales) <= allowed):

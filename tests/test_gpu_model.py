@@ -561,3 +561,67 @@ def test_plan_caches_share_a_byte_budget():
     r, c = m.detect_packed(imgs[0])
     torch.cuda.synchronize()
     assert torch.equal(c, first[1]) and all(torch.equal(r[i, :int(c[i])], first[0][i, :int(c[i])]) for i in range(2))
+
+
+def _rp_calls(plan):
+    """(FPN-output resident-patch calls, tower resident-patch calls) of a plan; a paired launch counts as its two calls."""
+    from dafne_amd import engine
+    fpn, towers = [], []
+    for c in plan.calls:
+        for cc in ((c.a, c.b) if isinstance(c, engine.ConvPairCall) else (c,)):
+            if isinstance(cc, engine.ConvCall) and cc.wfrag is not None:
+                (towers if hasattr(cc, "tower_tag") else fpn).append(cc)
+    return fpn, towers
+
+
+def test_one_resident_patch_form_per_model_whatever_the_environment_says_later(monkeypatch):
+    """The engine switches are fixed when a model packs its weights (P["options"]), not read per plan: R50 with
+    bench.build_model's seeded weights at 544 x 544 -- the smallest square multiple of 32 at which an FPN output layer
+    (fpn_output3, 68 x 68) is on conv3x3_rp beside the towers: it leaves conv_wr above 1250 pixels and reaches the patch kernel's
+    200 nominal tiles at ceil(68 / 8) * ceil(68 / 32) * 8 = 216; at 256 .. 512 the FPN outputs run on conv_wr / the generic tile.
+    A batch of 2 with the default form (16x16x32), then DAFNE_RP_MFMA16=0 and a batch of 3 whose first two images are the same:
+    the new plan still runs the 16x16x32 form from the same fragment weights, so the shared images keep their bits (the two forms
+    differ by up to 1 bf16 ulp).  A model built after the change uses the 32x32x16 form only."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    from dafne_amd import engine
+    monkeypatch.delenv("DAFNE_RP_MFMA16", raising=False)
+    S = 544
+    cfg, m, sd = bench.build_model(50, dev(), seed=0)
+    g = torch.Generator().manual_seed(77)
+    b3 = torch.randint(0, 256, (3, 3, S, S), generator=g, dtype=torch.uint8).to(dev())
+    r2, c2 = m.detect_packed(b3[:2].contiguous())
+    torch.cuda.synchronize()
+    r2, c2 = r2.clone(), c2.clone()
+    p2 = m.plan(2, S, S)
+    head2 = [t.clone() for t in p2.head.logits + p2.head.delta_ctr + p2.head.center]
+
+    monkeypatch.setenv("DAFNE_RP_MFMA16", "0")
+    assert (3, S, S) not in [k[:3] for k in m._plans]
+    r3, c3 = m.detect_packed(b3)
+    torch.cuda.synchronize()
+    p3 = m.plan(3, S, S)
+    assert p3 is not p2
+    P = m._weights()
+    assert P["options"].rp_mfma16 is True
+    assert not [k for k in P if k.endswith(".frag")] and [k for k in P if k.endswith(".frag16")]
+    for plan in (p2, p3):
+        assert "conv3x3_rp" in [c.kernel_name() for c in plan.calls]
+        fpn, towers = _rp_calls(plan)
+        assert len(fpn) >= 1 and len(towers) >= 12, (len(fpn), len(towers))
+        assert all(c.prm.flags & engine.F_FRAG16 for c in fpn + towers)
+    print("detections of the shared images:", c2.tolist())
+    assert torch.equal(c3[:2], c2)
+    for i in range(2):
+        assert torch.equal(r3[i, :int(c2[i])], r2[i, :int(c2[i])]), i
+    for a, b in zip(head2, p3.head.logits + p3.head.delta_ctr + p3.head.center):
+        assert torch.equal(a, b[:2])
+
+    cfg, fresh, _ = bench.build_model(50, dev(), seed=0)
+    pf = fresh.plan(2, S, S)
+    Pf = fresh._weights()
+    assert Pf["options"].rp_mfma16 is False
+    assert [k for k in Pf if k.endswith(".frag")] and not [k for k in Pf if k.endswith(".frag16")]
+    fpn, towers = _rp_calls(pf)
+    assert len(fpn) >= 1 and len(towers) >= 12 and not any(c.prm.flags & engine.F_FRAG16 for c in fpn + towers)
