@@ -159,6 +159,8 @@ SIGNATURES = {
     "dafne_bottleneck_body_scratch_bytes": (c_size_t, []),
     "dafne_bottleneck_body_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                           c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dafne_bottleneck_body16_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                            c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dafne_bottleneck_tail_head_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                                c_void_p, c_void_p, c_void_p]),
     "dafne_bottleneck_tail_head_narrow_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -162,6 +162,38 @@ static_assert(bn_wait<4>(0) == 7 && bn_wait<4>(1) == 8 && bn_wait<4>(7) == 14 &&
               bn_wait<2>(9) == 15 && bn_wait<2>(10) == 14 && bn_wait<2>(kStepsA + 16) == 15 && bn_wait<2>(kStepsA + 96 + 16) == 11,
               "vmcnt bookkeeping");
 
+// ---- the 16x16x32 form (conv_bneck_kernel<HEAD, TH, true>, dafne_bottleneck_body16_hip): the same tile, LDS layout, weight stream
+// and ping-pong with v_mfma_f32_16x16x32_bf16 -- half the accumulator traffic per flop (profiles/NOTES_r06.md; the towers' form:
+// conv.hip, conv3x3_rp_kernel<GNIN, true>).  A k32 group = the former k16 steps 2m, 2m + 1 (phase A: of one (slab, tap)).  Fragment
+// F(2m + cb) = output channels of MFMA rows 16 cb .. 16 cb + 15 of the wave x the 32 k of group m (lane: row lane & 15, k 8 (lane >> 4)
+// .. + 8); a B fragment = 16 pixels x those 32 k (lane: pixel lane & 15, the same k).  Step 2m + h multiplies BOTH fragments of its group
+// with pixel fragments kPF h .. kPF h + kPF - 1 (16 tile pixels each: tile row p >> 1, columns 16 (p & 1) ..), so a fragment lives for
+// two steps, and the ring of this form is TEN fragments deep: F(s + 9) is requested at the end of step s into slot (s + 9) % 10, the slot
+// of the fragment that died one step ago, and the even step of a pair waits for the pair's younger fragment, requested eight steps
+// before -- the cover of the 32x32x16 form, and its wait counts (7 in the steady state).  Measured in the plan, where a block's weights
+// come cold: a ring of 8 (five to six steps of cover) cost 4 % per launch, 10 and 12 are level with the 32x32x16 form
+// (profiles/NOTES_bneck_mfma16.md).  Still one 1-KiB load per step, and the same bn_post operations behind it.
+// Rows: a lane holds rows 4 (lane >> 4) + i of a 16-row fragment, so row 4a + i of fragment cb holds channel 8a + 4 cb + i of the wave's
+// 32 (engine.pack_bneck16): the lane's 4 + 4 values of a pixel fragment are ONE run of 8 consecutive channels -- the 16-byte piece
+// lane >> 4 of the pixel's 64 bytes.
+constexpr int kRing16 = 10, kDist16 = kRing16 - 1;
+template <int TH>
+constexpr int bn_wait16(int s) {                       // even s: the operations issued after F(s + 1) and before the wait of step s
+    int n = 0;
+    if (s + 1 < kDist16) {
+        n += kDist16 - 1 - (s + 1);                            // F(s + 2 .. kDist16 - 1) of the prologue
+        for (int u = 0; u < s; u++) n += 1 + bn_post<TH>(u);
+    } else {
+        n += bn_post<TH>(s + 1 - kDist16);                     // the operations right behind F(s + 1) at the end of step s + 1 - kDist16
+        for (int u = s + 2 - kDist16; u < s; u++) n += (u + kDist16 < kSteps ? 1 : 0) + bn_post<TH>(u);
+    }
+    return n;
+}
+static_assert(bn_wait16<4>(0) == 7 && bn_wait16<4>(2) == 9 && bn_wait16<4>(4) == 11 && bn_wait16<4>(6) == 13 && bn_wait16<4>(8) == 15 &&
+              bn_wait16<4>(20) == 7 && bn_wait16<4>(kStepsA + 16) == 23 && bn_wait16<4>(kStepsA + 22) == 23 && bn_wait16<4>(kStepsA + 24) == 7 &&
+              bn_wait16<4>(kSteps - 2) == 0 && bn_wait16<2>(kStepsA + 16) == 15 && bn_wait16<2>(kStepsA + 96 + 16) == 11,
+              "vmcnt bookkeeping (16x16x32 form)");
+
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) {
@@ -206,20 +238,46 @@ __device__ __forceinline__ void bn_bread(bf16x8 (&b)[PF], const unsigned (&pb)[3
     }
 }
 
-// phase B: the PF B fragments (pixel fragments 4096 B apart) of k16 step ST of the slab at byte offset OFF of the buffer at BUF
-template <int BUF, int OFF, int ST, int PF>
-__device__ __forceinline__ void bn_bread_b(bf16x8 (&b)[PF], const unsigned (&bs)[4], unsigned lds_base) {
-    const unsigned ad = lds_base + (unsigned)BUF + bs[ST];
-    constexpr int o = OFF;
+// the same in the 16x16x32 form: step J = group J >> 1 (k32 group kc2 of slab sl at tap (kh, kw)) x pixel fragments PF (J & 1) .. + PF - 1:
+// fragment f = patch row kh + (PF / 2) (J & 1) + (f >> 1), column half f & 1 (16 pixels = 2048 B on: the swizzle of column q + 16 is
+// that of q)
+template <int J, int PF, int PSLAB>
+__device__ __forceinline__ void bn_bread16(bf16x8 (&b)[PF], const unsigned (&pb)[3], unsigned lds_base) {
+    constexpr int sl = J / 36, t = J % 36, kh = t / 12, kw = (t >> 2) % 3, kc2 = (t >> 1) & 1;
+    const unsigned ad = lds_base + ((pb[kw] ^ (unsigned)(kc2 << 6)) + (unsigned)(sl * PSLAB));
+    constexpr int r0 = kh + (PF / 2) * (J & 1);
+    constexpr int o0 = r0 * kPC * 128, o1 = o0 + 2048, o2 = (r0 + 1) * kPC * 128, o3 = o2 + 2048;
+    static_assert(o3 <= 65535, "ds_read immediate");
     if constexpr (PF == 4) {
         asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8"
                      : "=&v"(b[0]), "=&v"(b[1]), "=&v"(b[2]), "=&v"(b[3])
-                     : "v"(ad), "n"(o), "n"(o + 4096), "n"(o + 8192), "n"(o + 12288)
+                     : "v"(ad), "n"(o0), "n"(o1), "n"(o2), "n"(o3)
+                     : "memory");
+    } else {
+        static_assert(PF == 2, "2 or 4 pixel fragments");
+        asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4"
+                     : "=&v"(b[0]), "=&v"(b[1])
+                     : "v"(ad), "n"(o0), "n"(o1)
+                     : "memory");
+    }
+}
+
+// phase B: the PF B fragments (pixel fragments STRIDE B apart: 32 pixels; 16x16x32 form: 16) of k step ST of the slab at byte offset
+// OFF of the buffer at BUF
+template <int BUF, int OFF, int ST, int PF, int STRIDE = 4096>
+__device__ __forceinline__ void bn_bread_b(bf16x8 (&b)[PF], const unsigned (&bs)[4], unsigned lds_base) {
+    const unsigned ad = lds_base + (unsigned)BUF + bs[ST];
+    constexpr int o = OFF;
+    static_assert(o + 3 * STRIDE <= 65535, "ds_read immediate");
+    if constexpr (PF == 4) {
+        asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8"
+                     : "=&v"(b[0]), "=&v"(b[1]), "=&v"(b[2]), "=&v"(b[3])
+                     : "v"(ad), "n"(o), "n"(o + STRIDE), "n"(o + 2 * STRIDE), "n"(o + 3 * STRIDE)
                      : "memory");
     } else {
         asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4"
                      : "=&v"(b[0]), "=&v"(b[1])
-                     : "v"(ad), "n"(o), "n"(o + 4096)
+                     : "v"(ad), "n"(o), "n"(o + STRIDE)
                      : "memory");
     }
 }
@@ -242,20 +300,30 @@ __device__ __forceinline__ void bn_wait_for(bf16x8 (&ar)[BN<TH>::kRing]) {
     asm volatile("s_waitcnt vmcnt(%1)" : "+v"(ar[J % kRing]) : "n"(kWaitN) : "memory");
 }
 
+template <int J, int TH>
+__device__ __forceinline__ void bn_wait16_for(bf16x8 (&ar)[kRing16]) {
+    static_assert((J & 1) == 0, "the even step of a pair waits");
+    constexpr int kWaitN = bn_wait16<TH>(J), kRing = kRing16;
+    static_assert(kWaitN < 64, "vmcnt is a 6-bit counter");
+    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(ar[J % kRing]), "+v"(ar[(J + 1) % kRing]) : "n"(kWaitN) : "memory");
+}
+
 // HEAD = false (the stage's last block: no next conv1): GEMM2 and the Z rows are skipped; the weight stream still
 // walks the (zero) conv1' fragments -- the vmcnt bookkeeping is one schedule for both forms.
-template <bool HEAD, int TH>
+// M16: the 16x16x32 form (above).
+template <bool HEAD, int TH, bool M16>
 __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
     typedef BN<TH> Geo;
     constexpr int kTH = Geo::kTH, kPx = Geo::kPx, kPPieces = Geo::kPPieces, kPP = Geo::kPP, kPSlab = Geo::kPSlab, kSlab = Geo::kSlab;
     constexpr int kOffY = Geo::kOffY, kOffT = Geo::kOffT, kOffPatch = Geo::kOffPatch, kOffBias = Geo::kOffBias;
-    constexpr int kPF = Geo::kPF, kRL = Geo::kRL, kTrickle = Geo::kTrickle, kRing = Geo::kRing;
+    constexpr int kPF = Geo::kPF, kRL = Geo::kRL, kTrickle = Geo::kTrickle, kRing = M16 ? kRing16 : Geo::kRing;
     static_assert(kPx == kTH * kTW, "tile");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int frow = lane & 31, half = lane >> 5;
+    // a lane's fragment row (its pixel in a B fragment) and its 8-wide piece of the fragment's k (16x16x32 form: 16 rows, 4 pieces)
+    const int frow = M16 ? (lane & 15) : (lane & 31), half = M16 ? (lane >> 4) : (lane >> 5);
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds;
 
     const int tile = xcd_remap(blockIdx.x, P.tiles);
@@ -336,7 +404,7 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
     // phase B: k16 step s inside a slab, pixel fragment 0 of a [128 px][128 B] slab
     unsigned bs[4];
 #pragma unroll
-    for (int s = 0; s < 4; s++) bs[s] = (unsigned)(frow * 128 + (((2 * s + half) ^ ((frow >> 1) & 7)) * 16));
+    for (int s = 0; s < 4; s++) bs[s] = (unsigned)(frow * 128 + ((((M16 ? 4 : 2) * s + half) ^ ((frow >> 1) & 7)) * 16));      // (16x16x32 form: k32 groups 0, 1)
     // phase A: patch row p (0..5) at tap column kw (0..2): pixel p * 34 + q, q = kw + frow; k16 step kc reads the 16-byte
     // chunk (2 kc + half) ^ sw, sw = (q >> 1) & 7 (the row pitch is even: a swizzle by COLUMN is conflict-free like one by
     // pixel index, and independent of the patch row).  That is  (pb[kw] ^ (kc << 5)) + p * 34 * 128  with
@@ -346,7 +414,9 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
     for (int kw = 0; kw < 3; kw++) {
         const int q = kw + frow;
         const int sw = (q >> 1) & 7;
-        pb[kw] = (unsigned)(kOffPatch + q * 128 + ((half ^ (sw & 1)) << 4) + ((sw >> 1) << 5));
+        // (16x16x32 form: the 32-channel group kc2 reads chunk (4 kc2 + half) ^ sw, i.e. (pb[kw] ^ (kc2 << 6)) + p * 34 * 128)
+        pb[kw] = M16 ? (unsigned)(kOffPatch + q * 128 + ((half ^ (sw & 3)) << 4) + ((sw >> 2) << 6))
+                     : (unsigned)(kOffPatch + q * 128 + ((half ^ (sw & 1)) << 4) + ((sw >> 1) << 5));
     }
 
     // ---- A operand: L2 -> registers through inline asm, ring of 8 k16 steps
@@ -356,9 +426,45 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
 #pragma unroll
     for (int k = 0; k < kRing; k++) ar[k] = bf16x8{};
     auto load_step = [&](auto J) { bn_load<decltype(J)::value, kRing>(ar, P.wf, voffA, voffB); };
-    auto wait_step = [&](auto J) { bn_wait_for<decltype(J)::value, TH>(ar); };
+    auto wait_step = [&](auto J) {
+        constexpr int j = decltype(J)::value;
+        if constexpr (!M16) bn_wait_for<j, TH>(ar);
+        else if constexpr ((j & 1) == 0) bn_wait16_for<j, TH>(ar);
+    };
+    constexpr int kDist = M16 ? kDist16 : kRing;           // a fragment is requested kDist steps ahead
 
-    f32x16 acc1[kPF], acc2[kPF];
+    // 64 accumulator registers per GEMM: kPF fragments of 32 x 32, or 2 kPF pixel fragments x 2 channel halves of 16 x 16
+    // (h[2 p + cb]: pixel fragment p, MFMA rows 16 cb ..)
+    f32x16 acc1[M16 ? 1 : kPF], acc2[M16 ? 1 : kPF];
+    f32x4 h1[M16 ? 4 * kPF : 1], h2[M16 ? 4 * kPF : 1];
+    auto zero_acc = [&](f32x16 (&a)[M16 ? 1 : kPF], f32x4 (&h)[M16 ? 4 * kPF : 1]) {
+        if constexpr (M16) {
+#pragma unroll
+            for (int b = 0; b < 4 * kPF; b++) h[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else {
+#pragma unroll
+            for (int b = 0; b < kPF; b++)
+#pragma unroll
+                for (int k = 0; k < 16; k++) a[b][k] = 0.f;
+        }
+    };
+    // the matrix instructions of step J on the B fragments in `bf`: one weight fragment x kPF pixel fragments of 32, or (16x16x32 form)
+    // the group's two fragments x kPF pixel fragments of 16
+    auto mma = [&](f32x16 (&a)[M16 ? 1 : kPF], f32x4 (&h)[M16 ? 4 * kPF : 1], const bf16x8 (&bf)[kPF], auto J) {
+        constexpr int j = decltype(J)::value;
+        const bf16x8(&ring)[kRing] = ar;
+        if constexpr (M16) {
+            constexpr int jb = j & ~1, p0 = kPF * (j & 1);
+#pragma unroll
+            for (int f = 0; f < kPF; f++)
+#pragma unroll
+                for (int cb = 0; cb < 2; cb++)
+                    h[2 * (p0 + f) + cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[(jb + cb) % kRing], bf[f], h[2 * (p0 + f) + cb], 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int b = 0; b < kPF; b++) a[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ring[j % kRing], bf[b], a[b], 0, 0, 0);
+        }
+    };
 
     auto barrier = [&]() {
         __builtin_amdgcn_sched_barrier(0);
@@ -404,6 +510,30 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
         constexpr int b = decltype(B)::value;
         asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(ad), "v"(v), "n"(b * 4096) : "memory");
     };
+    // ---- the same in the 16x16x32 form.  A lane holds, of pixel fragment p (16 pixels), channels 8 half + 0..7 of its wave's 32: h[2 p]
+    // the first four, h[2 p + 1] the last four -- ONE 16-byte piece per pixel fragment, at ey[0] + 2048 p (slab wave >> 1, pixel
+    // 16 p + frow, chunk (4 (wave & 1) + half) ^ ((frow >> 1) & 7): the expression of eoff with this form's frow and half)
+    auto bias8 = [&](int bias0, f32x4 (&bv)[2]) {                  // the lane's 8 biases
+        const unsigned bad = lbias_off + (unsigned)((bias0 + wave * 32 + 8 * half) * 4);
+        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)" : "=&v"(bv[0]), "=&v"(bv[1]) : "v"(bad) : "memory");
+    };
+    auto piece8 = [&](const f32x4& alo, const f32x4& ahi, const f32x4& blo, const f32x4& bhi, const u32x4& r) -> u32x4 {
+        u32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const unsigned rw = r[k];
+            const f32x2 rr = {__uint_as_float(rw << 16), __uint_as_float(rw & 0xffff0000u)};
+            const f32x2 aa = {k < 2 ? alo[2 * k] : ahi[2 * k - 4], k < 2 ? alo[2 * k + 1] : ahi[2 * k - 3]};
+            const f32x2 bb = {k < 2 ? blo[2 * k] : bhi[2 * k - 4], k < 2 ? blo[2 * k + 1] : bhi[2 * k - 3]};
+            const f32x2 v = aa + bb + rr;                           // (acc + bias) + residual, as above
+            o[k] = pack_bf16(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f));
+        }
+        return o;
+    };
+    auto lds_piece8 = [&](unsigned ad, const u32x4& v, auto PFR) {
+        constexpr int p = decltype(PFR)::value;
+        asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(ad), "v"(v), "n"(p * 2048) : "memory");
+    };
     // the wave's 8 KB of the buffer -> HBM rows in quad layout (LDS operations of one wave execute in order: the pieces this wave
     // wrote a moment ago are read back without a barrier), four instructions per LDS round trip
     auto rows_out = [&](char* base, size_t pix_bytes, const unsigned (&qc)[2], auto OFF) {
@@ -439,14 +569,17 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
     }
 #pragma unroll
     for (int ii = 0; ii < kPP; ii++) patch_piece(0, ii);
-    static_for<0, kRing>(load_step);
+    static_for<0, kDist>(load_step);
 
     // ================================================================ phase A: T = relu(conv2(U) + bias2)
-#pragma unroll
-    for (int b = 0; b < kPF; b++)
-#pragma unroll
-        for (int k = 0; k < 16; k++) acc1[b][k] = 0.f;
+    zero_acc(acc1, h1);
     bf16x8 bfr[2][kPF];
+    auto bread_a = [&](bf16x8 (&b)[kPF], auto J) {
+        const unsigned(&pq)[3] = pb;              // (non-dependent uses: a generic lambda captures the two only through them)
+        const unsigned lb = lds_base;
+        if constexpr (M16) bn_bread16<decltype(J)::value, kPF, kPSlab>(b, pq, lb);
+        else bn_bread<decltype(J)::value, kPF, kPSlab>(b, pq, lb);
+    };
     static_for<0, kStepsA>([&](auto J) {
         constexpr int j = decltype(J)::value;
         wait_step(J);
@@ -454,18 +587,17 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
         if constexpr (j == 35) barrier();            // slabs 1..3: every wave passed a wait covering its last piece at step 20
         // the B fragments of step j + 1 are requested before the MFMAs of step j (two register sets; the counted lgkmcnt leaves
         // exactly those four reads in flight)
-        if constexpr (j == 0) bn_bread<0, kPF, kPSlab>(bfr[0], pb, lds_base);
+        if constexpr (j == 0) bread_a(bfr[0], std::integral_constant<int, 0>{});
         if constexpr (j + 1 < kStepsA) {
-            bn_bread<j + 1, kPF, kPSlab>(bfr[(j + 1) & 1], pb, lds_base);
+            bread_a(bfr[(j + 1) & 1], std::integral_constant<int, j + 1>{});
             bn_bwait<kPF, false>(bfr[j & 1]);
         } else {
             bn_bwait<kPF, true>(bfr[j & 1]);
         }
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int r = 0; r < kPF; r++) acc1[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[j % kRing], bfr[j & 1][r], acc1[r], 0, 0, 0);
+        mma(acc1, h1, bfr[j & 1], J);
         __builtin_amdgcn_sched_barrier(0);
-        load_step(std::integral_constant<int, j + kRing>{});
+        load_step(std::integral_constant<int, j + kDist>{});
         if constexpr (j < kTrickle) patch_piece(1 + j / kPP, j % kPP);
         if constexpr (j >= kRes0 && j < kRes0 + kRL * kResStride && (j - kRes0) % kResStride == 0) {
             res_load(std::integral_constant<int, 0>{}, std::integral_constant<int, (j - kRes0) / kResStride>{});
@@ -473,7 +605,15 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
     });
     BN_STAMP();
     barrier();                                       // every wave is done with the patch: T may land on it
-    {
+    if constexpr (M16) {
+        f32x4 bv[2];
+        bias8(0, bv);
+        const unsigned et = ey[0] + (unsigned)(kOffT - kOffY);
+        static_for<0, 2 * kPF>([&](auto PFR) {
+            constexpr int p = decltype(PFR)::value;
+            lds_piece8(et, piece8(h1[2 * p], h1[2 * p + 1], bv[0], bv[1], u32x4{}), PFR);
+        });
+    } else {
         f32x4 bv[4];
         bias16(0, bv);
         const unsigned et[2] = {ey[0] + (unsigned)(kOffT - kOffY), ey[1] + (unsigned)(kOffT - kOffY)};
@@ -489,10 +629,16 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
     BN_STAMP();
 
     // ================================================================ phase B: the two-half ping-pong (see the top of the file)
-#pragma unroll
-    for (int b = 0; b < kPF; b++)
-#pragma unroll
-        for (int k = 0; k < 16; k++) acc2[b][k] = 0.f;
+    zero_acc(acc2, h2);
+    // the B fragments of step I of a GEMM segment whose first slab is Q0 of the buffer at BUF: k16 step I & 3 of slab Q0 + (I >> 2); 16x16x32
+    // form: k32 group (I >> 1) & 1 of that slab, pixel fragments kPF (I & 1) .. (2048 B apart)
+    auto bread_b = [&](bf16x8 (&b)[kPF], auto BUF, auto Q0, auto I) {
+        constexpr int buf = decltype(BUF)::value, q = decltype(Q0)::value + (decltype(I)::value >> 2), i = decltype(I)::value;
+        const unsigned(&bq)[4] = bs;              // (non-dependent uses: a generic lambda captures the two only through them)
+        const unsigned lb = lds_base;
+        if constexpr (M16) bn_bread_b<buf, q * kSlab + 2048 * kPF * (i & 1), (i >> 1) & 1, kPF, 2048>(b, bq, lb);
+        else bn_bread_b<buf, q * kSlab, i & 3, kPF>(b, bq, lb);
+    };
     const bool late = wave >= kNW / 2;               // wave-uniform: waves 4..7 run one segment behind their SIMD mates
     if (late) barrier();
     static_for<0, kChunks>([&](auto C) {
@@ -512,26 +658,24 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
             asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(qa), "v"(rr[k]), "n"(k * 2048) : "memory");
         });
         // ---- G1(c): acc1 = W3[c] . T  (K = 256 over the four slabs of the T tile)
-#pragma unroll
-        for (int b = 0; b < kPF; b++)
-#pragma unroll
-            for (int k = 0; k < 16; k++) acc1[b][k] = 0.f;
+        zero_acc(acc1, h1);
         static_for<0, 16>([&](auto I) {
             constexpr int i = decltype(I)::value;
             constexpr int j = j0 + i;
+            constexpr std::integral_constant<int, kOffT> T{};
+            constexpr std::integral_constant<int, 0> Q0{};
             wait_step(std::integral_constant<int, j>{});
-            if constexpr (i == 0) bn_bread_b<kOffT, 0, 0, kPF>(bfr[j & 1], bs, lds_base);
+            if constexpr (i == 0) bread_b(bfr[j & 1], T, Q0, I);
             if constexpr (i + 1 < 16) {
-                bn_bread_b<kOffT, ((i + 1) >> 2) * kSlab, ((i + 1) & 3), kPF>(bfr[(j + 1) & 1], bs, lds_base);
+                bread_b(bfr[(j + 1) & 1], T, Q0, std::integral_constant<int, i + 1>{});
                 bn_bwait<kPF, false>(bfr[j & 1]);
             } else {
                 bn_bwait<kPF, true>(bfr[j & 1]);
             }
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int b = 0; b < kPF; b++) acc1[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[j % kRing], bfr[j & 1][b], acc1[b], 0, 0, 0);
+            mma(acc1, h1, bfr[j & 1], std::integral_constant<int, j>{});
             __builtin_amdgcn_sched_barrier(0);
-            load_step(std::integral_constant<int, j + kRing>{});
+            load_step(std::integral_constant<int, j + kDist>{});
         });
         barrier();
         if constexpr (c == 0) BN_STAMP();
@@ -540,25 +684,44 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
         // them (the K operand of conv1'), then the 8 KB read back in quad layout and stored
         {
             if constexpr (c + 1 < kChunks) static_for<0, kRL>([&](auto K) { res_load(std::integral_constant<int, c + 1>{}, K); });
-            f32x4 bv[4];
-            bias16(256 + c * 256, bv);
-            static_for<0, kPF / 2>([&](auto BP) {
-                constexpr int b0 = 2 * decltype(BP)::value;
-                const unsigned e0 = ey[0], e1 = ey[1];
-                u32x4 r[4];
-                asm volatile("ds_read_b128 %0, %4 offset:%6\n\tds_read_b128 %1, %5 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %5 offset:%7\n\t"
-                             "s_waitcnt lgkmcnt(0)"
-                             : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
-                             : "v"(e0), "v"(e1), "n"(b0 * 4096), "n"((b0 + 1) * 4096)
-                             : "memory");
-                static_for<0, 2>([&](auto BB) {
-                    constexpr int b = b0 + decltype(BB)::value;
-                    static_for<0, 2>([&](auto RUN) {
-                        constexpr int run = decltype(RUN)::value;
-                        lds_piece(ey[run], piece(acc1[b], RUN, bv[2 * run], bv[2 * run + 1], r[2 * (b - b0) + run]), std::integral_constant<int, b>{});
+            f32x4 bv[M16 ? 2 : 4];
+            if constexpr (M16) {
+                // four pixel fragments per LDS round trip: their residual pieces in, the y pieces over them
+                bias8(256 + c * 256, bv);
+                static_for<0, kPF / 2>([&](auto PG) {
+                    constexpr int p0 = 4 * decltype(PG)::value;
+                    const unsigned e0 = ey[0];
+                    u32x4 r[4];
+                    asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8\n\t"
+                                 "s_waitcnt lgkmcnt(0)"
+                                 : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
+                                 : "v"(e0), "n"(p0 * 2048), "n"((p0 + 1) * 2048), "n"((p0 + 2) * 2048), "n"((p0 + 3) * 2048)
+                                 : "memory");
+                    static_for<0, 4>([&](auto PP) {
+                        constexpr int p = p0 + decltype(PP)::value;
+                        lds_piece8(ey[0], piece8(h1[2 * p], h1[2 * p + 1], bv[0], bv[1], r[p - p0]), std::integral_constant<int, p>{});
                     });
                 });
-            });
+            } else {
+                bias16(256 + c * 256, bv);
+                static_for<0, kPF / 2>([&](auto BP) {
+                    constexpr int b0 = 2 * decltype(BP)::value;
+                    const unsigned e0 = ey[0], e1 = ey[1];
+                    u32x4 r[4];
+                    asm volatile("ds_read_b128 %0, %4 offset:%6\n\tds_read_b128 %1, %5 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %5 offset:%7\n\t"
+                                 "s_waitcnt lgkmcnt(0)"
+                                 : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
+                                 : "v"(e0), "v"(e1), "n"(b0 * 4096), "n"((b0 + 1) * 4096)
+                                 : "memory");
+                    static_for<0, 2>([&](auto BB) {
+                        constexpr int b = b0 + decltype(BB)::value;
+                        static_for<0, 2>([&](auto RUN) {
+                            constexpr int run = decltype(RUN)::value;
+                            lds_piece(ey[run], piece(acc1[b], RUN, bv[2 * run], bv[2 * run + 1], r[2 * (b - b0) + run]), std::integral_constant<int, b>{});
+                        });
+                    });
+                });
+            }
             rows_out(P.out, (size_t)(kCB * 2), qcx, std::integral_constant<int, c * 512>{});
         }
         barrier();
@@ -569,22 +732,22 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
             static_for<0, 8>([&](auto I) {
                 constexpr int i = decltype(I)::value;
                 constexpr int j = j0 + 16 + 8 * hh + i;
-                constexpr int q = 2 * hh + (i >> 2), st = i & 3;
+                constexpr std::integral_constant<int, kOffY> Y{};
+                constexpr std::integral_constant<int, 2 * hh> Q0{};
                 wait_step(std::integral_constant<int, j>{});
                 if constexpr (HEAD) {
-                    if constexpr (i == 0) bn_bread_b<kOffY, q * kSlab, st, kPF>(bfr[j & 1], bs, lds_base);
+                    if constexpr (i == 0) bread_b(bfr[j & 1], Y, Q0, I);
                     if constexpr (i + 1 < 8) {
-                        bn_bread_b<kOffY, (2 * hh + ((i + 1) >> 2)) * kSlab, ((i + 1) & 3), kPF>(bfr[(j + 1) & 1], bs, lds_base);
+                        bread_b(bfr[(j + 1) & 1], Y, Q0, std::integral_constant<int, i + 1>{});
                         bn_bwait<kPF, false>(bfr[j & 1]);
                     } else {
                         bn_bwait<kPF, true>(bfr[j & 1]);
                     }
                     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int b = 0; b < kPF; b++) acc2[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[j % kRing], bfr[j & 1][b], acc2[b], 0, 0, 0);
+                    mma(acc2, h2, bfr[j & 1], std::integral_constant<int, j>{});
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                load_step(std::integral_constant<int, j + kRing>{});
+                load_step(std::integral_constant<int, j + kDist>{});
             });
             // Every wave, also behind G2b(3).  For waves 4..7 that last barrier has no partner among waves 0..3, which are one
             // segment ahead: through their Z rows and gone, or about to be -- s_barrier waits for the surviving waves of a
@@ -601,15 +764,24 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
     // ---- Z = relu(acc2 + bias1): through the wave's 8 KB of the Y buffer (free: its last readers were G2a(3) / G2b(3)) into quad
     // layout and out (waves 0..3 beside G2b(3) of waves 4..7)
     if constexpr (HEAD) {
-        f32x4 bv[4];
-        bias16(256 + kCB, bv);
-        static_for<0, kPF>([&](auto B) {
-            constexpr int b = decltype(B)::value;
-            static_for<0, 2>([&](auto RUN) {
-                constexpr int run = decltype(RUN)::value;
-                lds_piece(ey[run], piece(acc2[b], RUN, bv[2 * run], bv[2 * run + 1], u32x4{}), B);
+        if constexpr (M16) {
+            f32x4 bv[2];
+            bias8(256 + kCB, bv);
+            static_for<0, 2 * kPF>([&](auto PFR) {
+                constexpr int p = decltype(PFR)::value;
+                lds_piece8(ey[0], piece8(h2[2 * p], h2[2 * p + 1], bv[0], bv[1], u32x4{}), PFR);
             });
-        });
+        } else {
+            f32x4 bv[4];
+            bias16(256 + kCB, bv);
+            static_for<0, kPF>([&](auto B) {
+                constexpr int b = decltype(B)::value;
+                static_for<0, 2>([&](auto RUN) {
+                    constexpr int run = decltype(RUN)::value;
+                    lds_piece(ey[run], piece(acc2[b], RUN, bv[2 * run], bv[2 * run + 1], u32x4{}), B);
+                });
+            });
+        }
         rows_out(P.next, (size_t)(kCM * 2), qcz, std::integral_constant<int, 0>{});
     }
 #ifdef DAFNE_BNECK_TIMING
@@ -624,15 +796,17 @@ __global__ void __launch_bounds__(512, 2) conv_bneck_kernel(BneckDev P) {
 #endif
 }
 
-}  // namespace
+template <int TH, bool M16>
+int bneck_launch(const BneckDev& D, bool head, hipStream_t stream) {
+    DAFNE_MAX_LDS_ONCE(BN<TH>::kSmemTotal, (const void*)conv_bneck_kernel<true, TH, M16>, (const void*)conv_bneck_kernel<false, TH, M16>);
+    if (head) hipLaunchKernelGGL((conv_bneck_kernel<true, TH, M16>), dim3(D.tiles), dim3(kNT), BN<TH>::kSmemTotal, stream, D);
+    else hipLaunchKernelGGL((conv_bneck_kernel<false, TH, M16>), dim3(D.tiles), dim3(kNT), BN<TH>::kSmemTotal, stream, D);
+    return DAFNE_OK;
+}
 
-extern "C" {
-
-size_t dafne_bottleneck_body_scratch_bytes(void) { return (size_t)kDumpBytes; }
-
-int dafne_bottleneck_body_hip(const void* d_in, const void* d_res, const void* d_wfrag, const float* d_bias2,
-                              const float* d_bias3, const float* d_bias1, int n_images, int H, int W, void* d_out,
-                              void* d_next, void* d_scratch, size_t scratch_bytes, void* stream) {
+// both exports: m16 = the 16x16x32 form (d_wfrag in engine.pack_bneck16's order)
+int bneck_body(const void* d_in, const void* d_res, const void* d_wfrag, const float* d_bias2, const float* d_bias3, const float* d_bias1,
+               int n_images, int H, int W, void* d_out, void* d_next, void* d_scratch, size_t scratch_bytes, void* stream, bool m16) {
     const bool head = d_next != nullptr;
     if (!d_in || !d_res || !d_wfrag || !d_bias2 || !d_bias3 || (head && !d_bias1) || !d_out || !d_scratch)
         return dafne::fail(DAFNE_E_INVALID, "bottleneck_body: null argument");
@@ -662,16 +836,29 @@ int dafne_bottleneck_body_hip(const void* d_in, const void* d_res, const void* d
     if (tiles > (1ll << 24) || pix * (kCB * 2) > 0xffffffffll) return dafne::fail(DAFNE_E_UNSUPPORTED, "bottleneck_body: too large");
     D.tiles = (int)tiles;
     D.max_pix = (unsigned)(pix - 1);
-    if (th == 4) {
-        DAFNE_MAX_LDS_ONCE(BN<4>::kSmemTotal, (const void*)conv_bneck_kernel<true, 4>, (const void*)conv_bneck_kernel<false, 4>);
-        if (head) hipLaunchKernelGGL((conv_bneck_kernel<true, 4>), dim3(D.tiles), dim3(kNT), BN<4>::kSmemTotal, (hipStream_t)stream, D);
-        else hipLaunchKernelGGL((conv_bneck_kernel<false, 4>), dim3(D.tiles), dim3(kNT), BN<4>::kSmemTotal, (hipStream_t)stream, D);
-    } else {
-        DAFNE_MAX_LDS_ONCE(BN<2>::kSmemTotal, (const void*)conv_bneck_kernel<true, 2>, (const void*)conv_bneck_kernel<false, 2>);
-        if (head) hipLaunchKernelGGL((conv_bneck_kernel<true, 2>), dim3(D.tiles), dim3(kNT), BN<2>::kSmemTotal, (hipStream_t)stream, D);
-        else hipLaunchKernelGGL((conv_bneck_kernel<false, 2>), dim3(D.tiles), dim3(kNT), BN<2>::kSmemTotal, (hipStream_t)stream, D);
-    }
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = th == 4 ? (m16 ? bneck_launch<4, true>(D, head, st) : bneck_launch<4, false>(D, head, st))
+                         : (m16 ? bneck_launch<2, true>(D, head, st) : bneck_launch<2, false>(D, head, st)))
+        return rc;
     return dafne::check_launch("conv_bneck");
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dafne_bottleneck_body_scratch_bytes(void) { return (size_t)kDumpBytes; }
+
+int dafne_bottleneck_body_hip(const void* d_in, const void* d_res, const void* d_wfrag, const float* d_bias2,
+                              const float* d_bias3, const float* d_bias1, int n_images, int H, int W, void* d_out,
+                              void* d_next, void* d_scratch, size_t scratch_bytes, void* stream) {
+    return bneck_body(d_in, d_res, d_wfrag, d_bias2, d_bias3, d_bias1, n_images, H, W, d_out, d_next, d_scratch, scratch_bytes, stream, false);
+}
+
+int dafne_bottleneck_body16_hip(const void* d_in, const void* d_res, const void* d_wfrag, const float* d_bias2,
+                                const float* d_bias3, const float* d_bias1, int n_images, int H, int W, void* d_out,
+                                void* d_next, void* d_scratch, size_t scratch_bytes, void* stream) {
+    return bneck_body(d_in, d_res, d_wfrag, d_bias2, d_bias3, d_bias1, n_images, H, W, d_out, d_next, d_scratch, scratch_bytes, stream, true);
 }
 
 }  // extern "C"

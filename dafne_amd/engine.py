@@ -250,6 +250,43 @@ def pack_bneck(w2, w3, w1):
     return torch.cat([a0.contiguous().reshape(-1), pb]).contiguous()
 
 
+def _bneck_row_perm16(device):
+    """The 16x16 counterpart of _bneck_row_perm (conv_bneck.hip's 16x16x32 form): a wave's 32 output channels are two fragments
+    of 16 MFMA rows and a lane holds rows 4a + i (a = lane >> 4, i = 0..3) of both, so row 4a + i of fragment cb holds channel
+    8a + 4cb + i -- the lane's 4 + 4 accumulator registers of a pixel fragment are ONE run of 8 consecutive channels, one 16-byte
+    piece of the pixel's row.  -> perm[16cb + 4a + i]."""
+    r = torch.arange(32, device=device)
+    cb, a, i = r >> 4, (r >> 2) & 3, r & 3
+    return 8 * a + 4 * cb + i
+
+
+def pack_bneck16(w2, w3, w1):
+    """Fragment-major weights of dafne_bottleneck_body16_hip (the 16x16x32 form): pack_bneck's sections and sizes with 1-KiB
+    fragments of 16 rows x 32 k.  conv2: [8 waves][144 fragments][64 lanes][8], fragment 2m + cb = rows wave*32 +
+    perm16[16cb + (lane & 15)], K columns 32m + 8*(lane >> 4) .. +8 (pack_conv's K order: k32 group m = two k16 steps of one slab
+    and tap); then [8 GEMMs][8 waves][16 fragments][64 lanes][8]: GEMM 2c = conv3 rows c*256 + wave*32 + perm16[..] over K = 256,
+    GEMM 2c+1 = conv1 rows wave*32 + perm16[..] over K-chunk c, fragment 2m + cb as above."""
+    assert tuple(w2.shape) == (256, 2304) and w2.dtype == BF16
+    assert tuple(w3.shape) == (1024, 256) and tuple(w1.shape) == (256, 1024) and w3.dtype == BF16 and w1.dtype == BF16
+    perm = _bneck_row_perm16(w2.device)
+    a0 = w2.reshape(8, 32, 72, 4, 8)[:, perm].reshape(8, 2, 16, 72, 4, 8).permute(0, 3, 1, 4, 2, 5)                # w, m, cb, q, r, e
+    a1 = w3.reshape(4, 8, 32, 8, 4, 8)[:, :, perm].reshape(4, 8, 2, 16, 8, 4, 8).permute(0, 1, 4, 2, 5, 3, 6)      # c, w, m, cb, q, r, e
+    a2 = w1.reshape(8, 32, 4, 8, 4, 8)[:, perm].reshape(8, 2, 16, 4, 8, 4, 8).permute(3, 0, 4, 1, 5, 2, 6)         # c, w, m, cb, q, r, e
+    pb = torch.stack([a1, a2], dim=1).contiguous().reshape(-1)
+    return torch.cat([a0.contiguous().reshape(-1), pb]).contiguous()
+
+
+def bneck_weights(P, key, w2, w3, w1):
+    """The fused res4 block's weights of P[key + "bneck"], packed on first use in the ONE form P["options"] dictates (rp_mfma16:
+    the resident-operand kernels' matrix instruction) -> (wfrag, mfma16)."""
+    f16 = P["options"].rp_mfma16
+    fkey, other = (key + "bneck16", key + "bneck") if f16 else (key + "bneck", key + "bneck16")
+    assert other not in P, "one conv_bneck form per model: %s" % other
+    if fkey not in P:
+        P[fkey] = pack_bneck16(w2, w3, w1) if f16 else pack_bneck(w2, w3, w1)
+    return P[fkey], f16
+
+
 def pack_conv3x3_frag(w):
     """Fragment-major weights of dafne_conv3x3_c256_hip from a packed 3x3 weight ([Cout, 2304] bf16, pack_conv's K order):
     bf16 [Cout/256][8 waves][144 k16 steps][64 lanes][8]: rows nt*256 + wave*32 + (lane & 31), K columns 16*step +
@@ -762,9 +799,10 @@ class DensePlan:
                     # res4: conv2 (3x3) + conv3 + residual + ReLU + the next block's conv1 + ReLU in ONE kernel
                     # (conv_bneck.hip): neither the 3x3's output nor conv3's is read back from HBM
                     w1, b1 = P[nxt] if bn_head else (torch.zeros(256, 1024, dtype=BF16, device=w2.device), None)
-                    key = p + "bneck"
-                    if key not in P:
-                        P[key] = pack_bneck(w2, w3, w1)
+                    # in the model's ONE matrix-instruction form (opt.rp_mfma16: 16x16x32, <= 1 bf16 ulp from the separate launches;
+                    # off: 32x32x16, bit-identical to them): every plan of a model, at any batch size, runs the same one
+                    wbn, bn16 = bneck_weights(P, p, w2, w3, w1)
+                    body_fn = L.dafne_bottleneck_body16_hip if bn16 else L.dafne_bottleneck_body_hip
                     if bneck_scratch is None:
                         bneck_scratch = torch.empty(L.dafne_bottleneck_body_scratch_bytes(), dtype=torch.uint8, device=device)
                     inpl = res_dead(sc, x, b)
@@ -772,11 +810,11 @@ class DensePlan:
                     y1_next = pool.get(n, y1.h, y1.w, 256) if bn_head else None
                     fl = 2 * n * y1.h * y1.w * (256 * 2304 + 256 * 1024 + (1024 * 256 if bn_head else 0))
                     nb_ = n * y1.h * y1.w * (256 + 1024 + 1024 + (256 if bn_head else 0)) * 2 + (256 * 2304 + 2 * 1024 * 256) * 2
-                    self.calls.append(FnCall(L.dafne_bottleneck_body_hip,
-                                             (_lib.ptr(y1.t), _lib.ptr(sc.t), _lib.ptr(P[key]), _lib.ptr(b2), _lib.ptr(b3), _lib.ptr(b1),
+                    self.calls.append(FnCall(body_fn,
+                                             (_lib.ptr(y1.t), _lib.ptr(sc.t), _lib.ptr(wbn), _lib.ptr(b2), _lib.ptr(b3), _lib.ptr(b1),
                                               n, y1.h, y1.w, _lib.ptr(y3.t), _lib.ptr(y1_next.t) if bn_head else None, _lib.ptr(bneck_scratch),
                                               bneck_scratch.numel()),
-                                             (y1, sc, P[key], b2, b3, b1, y3, y1_next, bneck_scratch),
+                                             (y1, sc, wbn, b2, b3, b1, y3, y1_next, bneck_scratch),
                                              "conv_bneck" if bn_head else "conv_bneck_last", flops=fl, nbytes=nb_))
                     self.flops += fl
                     pool.put(y1)

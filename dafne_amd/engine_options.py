@@ -18,7 +18,8 @@ def _switch(env, default, only_1=False):
 
 @dataclass(frozen=True)
 class EngineOptions:
-    # bits (<= 1 bf16 ulp): conv3x3_rp's matrix instruction, 16x16x32 (weights pack_conv3x3_frag16, flag F_FRAG16); off: 32x32x16
+    # bits (<= 1 bf16 ulp per layer): the resident-operand kernels' matrix instruction: towers and res4.  16x16x32 (conv3x3_rp: weights
+    # pack_conv3x3_frag16, flag F_FRAG16; conv_bneck: weights pack_bneck16, dafne_bottleneck_body16_hip); off: 32x32x16 in both
     rp_mfma16: bool = _switch("DAFNE_RP_MFMA16", True)
     # launches: the 256-channel 3x3 layers (towers, FPN outputs) on conv3x3_rp; off: conv3x3_patch
     conv_rp: bool = _switch("DAFNE_CONV_RP", True)
@@ -40,7 +41,8 @@ class EngineOptions:
     fuse_b2b_narrow: bool = _switch("DAFNE_FUSE_B2B_NARROW", True)
     # launches: the same pair in res3 (conv_b2b_mid)
     fuse_b2b_mid: bool = _switch("DAFNE_FUSE_B2B_MID", True)
-    # launches: res4's conv2 + conv3 + residual + next conv1 in one kernel (conv_bneck)
+    # launches: res4's conv2 + conv3 + residual + next conv1 in one kernel (conv_bneck).  While rp_mfma16 is on the kernel runs its
+    # 16x16x32 form, so 0 (the separate 32x32x16 launches) then also changes res4's bits; likewise fuse_bneck_last for the last block
     fuse_bneck: bool = _switch("DAFNE_FUSE_BNECK", True)
     # launches: a whole res3 block in one kernel (conv_blk_mid)
     fuse_blk_mid: bool = _switch("DAFNE_FUSE_BLK_MID", True)

@@ -430,6 +430,20 @@ int dafne_bottleneck_body_hip(const void* d_in, const void* d_res, const void* d
                               const float* d_bias3, const float* d_bias1, int n_images, int H, int W, void* d_out,
                               void* d_next, void* d_scratch, size_t scratch_bytes, void* stream);
 /*
+ * The same kernel with v_mfma_f32_16x16x32_bf16 at its three GEMM sites (ABI 150; the towers' DAFNE_CONV_FRAG16 for res4: half the
+ * accumulator traffic per flop).  Same arguments, sizes, tile choice and scratch; d_wfrag in engine.pack_bneck16's order: the same
+ * sections and byte counts as above with 1-KiB fragments of 16 rows x 32 k -- fragment 2m + cb of a wave = rows wave*32 +
+ * perm16[16 cb + (lane & 15)], K columns 32m + 8*(lane >> 4) .. +8 (conv2: 144 fragments per wave, k32 group m = the k16 steps 2m,
+ * 2m + 1 of one slab and tap; each GEMM of conv3 / conv1': 16 fragments per wave), perm16[16 cb + 4a + i] = 8a + 4 cb + i  (cb = 0..1,
+ * a = 0..3, i = 0..3): a lane's 4 + 4 accumulator registers of a 16-pixel fragment are one run of 8 consecutive channels.  Every
+ * output is the same products summed in another order: at most 1 bf16 ulp from dafne_bottleneck_body_hip on an output whose sum
+ * does not cancel, NOT bit-identical to it; identical from run to run, at any batch size and tile height.  A model runs ONE of the
+ * two entries for all its res4 blocks (engine: EngineOptions.rp_mfma16).
+ */
+int dafne_bottleneck_body16_hip(const void* d_in, const void* d_res, const void* d_wfrag, const float* d_bias2,
+                                const float* d_bias3, const float* d_bias1, int n_images, int H, int W, void* d_out,
+                                void* d_next, void* d_scratch, size_t scratch_bytes, void* stream);
+/*
  * The same pair for the narrow stage res2 (same reference block):  d_out = relu(conv3(d_in) + bias3 + d_res)  (1x1,
  * 64 -> 256; d_res = the block's shortcut: the identity input or the projection's output) and
  * d_next = relu(conv1'(d_out) + bias1)  (1x1, 256 -> 64).  d_in / d_next [N,H+2,W+2,64], d_res / d_out [N,H+2,W+2,256],
