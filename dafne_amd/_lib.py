@@ -209,6 +209,11 @@ SIGNATURES = {
     "dafne_assign_targets_hip": (c_int, [ctypes.POINTER(TargetParams)] + [c_void_p] * 5 + [c_int] + [c_void_p] * 6),
     "dafne_losses_workspace_bytes": (c_size_t, [ctypes.POINTER(LossParams), ctypes.POINTER(LevelDesc)]),
     "dafne_losses_hip": (c_int, [ctypes.POINTER(LossParams), ctypes.POINTER(LevelDesc)] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "dafne_scene_split_labels_hip": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                             c_double, c_double, c_double, c_void_p, c_i64, c_void_p]),
+    "dafne_scene_pack_tile_gt_workspace_bytes": (c_size_t, [c_int]),
+    "dafne_scene_pack_tile_gt_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double, c_double, c_int] +
+                                     [c_void_p] * 13 + [c_size_t, c_void_p]),
 }
 
 

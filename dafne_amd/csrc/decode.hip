@@ -779,3 +779,6 @@ int dafne_tta_candidates_hip(const dafne_tta_view* views, int n_views, int n_ima
 
 // ------------------------------------------------ target assignment and loss values (dafne_assign_targets_hip, dafne_losses_hip)
 #include "targets_kernels.h"
+
+// ------------------------------------------------ scene labels -> tile ground truth (dafne_scene_split_labels_hip, dafne_scene_pack_tile_gt_hip)
+#include "scene_labels_kernels.h"

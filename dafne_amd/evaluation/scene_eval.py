@@ -33,27 +33,30 @@ def load_scene_labels(label_dir, scene_names, classnames, parse_gt=dota_evaluati
     """One `<label_dir>/<scene>.txt` per scene (a missing file raises FileNotFoundError naming it); objects of classes outside
     `classnames` are dropped, as voc_eval never looks at them.  -> {"boxes" [G,8] f64, "offsets" [S*C+1] int32, "difficult"
     [G] bool, "npos" [S,C] int64 (non-difficult boxes per scene and class), "npos_class" [C], "scene_names", "classnames"}:
-    boxes sorted bucket-major (bucket = scene * C + class), file order inside a bucket."""
+    boxes sorted bucket-major (bucket = scene * C + class), file order inside a bucket.  Two more keys carry what the bucket
+    order loses, for scene_labels.split_scene_labels: "file_index" [G] int32, the object's position among the parsed objects of
+    its scene's file (the order ImgSplit walks them in), and "difficult_value" [G] int32, the difficult field as written."""
     classnames = list(classnames)
     index = {c: k for k, c in enumerate(classnames)}
     S, C = len(scene_names), len(classnames)
-    boxes, difficult, counts = [], [], np.zeros(S * C, dtype=np.int64)
+    boxes, difficult, file_index, counts = [], [], [], np.zeros(S * C, dtype=np.int64)
     npos = np.zeros((S, C), dtype=np.int64)
     for s, name in enumerate(scene_names):
         path = os.path.join(label_dir, "%s.txt" % name)
         if not os.path.isfile(path):
             raise FileNotFoundError("scene labels: no label file for scene %r: %s" % (name, path))
         per_class = [[] for _ in range(C)]
-        for o in parse_gt(path):
+        for pos, o in enumerate(parse_gt(path)):
             k = index.get(o["name"])
             if k is not None:
-                per_class[k].append(o)
+                per_class[k].append((pos, o))
         for k, objs in enumerate(per_class):
             counts[s * C + k] = len(objs)
-            for o in objs:
+            for pos, o in objs:
                 boxes.append(o["bbox"])
                 difficult.append(o["difficult"])
-            npos[s, k] = sum(1 for o in objs if not bool(o["difficult"]))
+                file_index.append(pos)
+            npos[s, k] = sum(1 for _, o in objs if not bool(o["difficult"]))
     G = len(boxes)
     if G >= 2 ** 31:
         raise ValueError("scene labels: %d boxes overflow the int32 offsets" % G)
@@ -61,7 +64,9 @@ def load_scene_labels(label_dir, scene_names, classnames, parse_gt=dota_evaluati
     offsets[1:] = np.cumsum(counts)
     return {"boxes": np.asarray(boxes, dtype=np.float64).reshape(G, 8), "offsets": offsets,
             "difficult": np.asarray(difficult).astype(bool).reshape(G), "npos": npos, "npos_class": npos.sum(0),
-            "scene_names": list(scene_names), "classnames": classnames}
+            "scene_names": list(scene_names), "classnames": classnames,
+            "file_index": np.asarray(file_index, dtype=np.int32).reshape(G),
+            "difficult_value": np.asarray(difficult, dtype=np.int32).reshape(G)}
 
 
 def rec4(boxes):

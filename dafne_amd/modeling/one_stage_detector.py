@@ -820,6 +820,19 @@ class OneStageDetector(nn.Module):
         self._last_validation = {"plan": plan, "targets": tg, "extras": extras}      # (tests: what the values were computed from)
         return losses
 
+    def validation_losses_scenes(self, scenes, labels, patch_size=1024, overlap=200, batch=8, layout_hwc=None, filter_empty=True):
+        """validation_losses on whole scenes and their scene-level labelTxt (evaluation.scene_eval.load_scene_labels, what
+        score_scenes reads): the labels are split into the ground truth of every tile on the device (scene_labels.
+        split_scene_labels: ImgSplit's tile labels, then the DOTA2COCO / load_dota_json filters with INPUT.MIN_AREA / MIN_SIDE),
+        tiles without a kept object are dropped when filter_empty (detectron2's DATALOADER.FILTER_EMPTY_ANNOTATIONS default),
+        the remaining tiles are cut with scene.gather_tiles, resized as detect_scenes resizes them, and go through
+        validation_losses in batches of `batch`.  -> {"loss/...": the batch-size-weighted mean of every term (float), "tiles":
+        how many tiles were run, "tile_ids": which ones, in split order over the scenes}.  Rate 1 only.  Raises on a CPU scene,
+        under self.training, and when no tile is left."""
+        from .. import scene_labels
+        return scene_labels.validation_losses_scenes(self, scenes, labels, patch_size=patch_size, overlap=overlap, batch=batch,
+                                                     layout_hwc=layout_hwc, filter_empty=filter_empty)
+
     def inference(self, batched_inputs, detected_instances=None, do_postprocess=True):
         assert not self.training
         return self.forward(batched_inputs, do_postprocess)

@@ -829,6 +829,35 @@ int dafne_losses_hip(const dafne_loss_params* prm, const dafne_level_desc* level
                      const float* d_reg_corners, const float* d_reg_ltrb, const float* d_reg_abcd, double* d_out6,
                      float* d_ctr_targets, void* d_ws, size_t ws_bytes, void* stream);
 
+/*
+ * Scene labels -> the ground truth of every tile of a split scene (ImgSplit_multi_process.splitbase.savepatches at rate 1
+ * for convex quadrilaterals, then the training filter of DOTA2COCO.py / dafne/data/datasets/dota.py); the operation order
+ * is written down in csrc/scene_labels_kernels.h.
+ * dafne_scene_split_labels_hip: one thread per (tile, object of its scene) pair.  d_tiles5 [T, 5] int32 = scene, left, up,
+ * right, down (right = min(left + patch, w - 1), down = min(up + patch, h - 1): SplitSingle's rectangle); d_pair_off
+ * [T + 1] int32: pair p of tile t is object d_obj_off[scene] + (p - d_pair_off[t]); d_obj_off [S + 1]; d_boxes [G, 8] f64 and
+ * d_difficult [G] int32 in label-file order per scene.  d_records [P, 12] int32: outcome (0 none, 1 inside, 2 cut to 4
+ * vertices, 3 cut to 5, 4 dropped with < 4, 5 dropped with > 5, 6 non-convex object), the 8 tile coordinates, difficult
+ * (2: the part left is <= thresh of the object), kept (passes difficult != 2, area > min_area, max side >= min_side, no
+ * coinciding corners), 0.  n_pairs above INT32_MAX is refused.
+ * dafne_scene_pack_tile_gt_hip: ordered compaction per tile (count, exclusive scan over tiles, write; no atomics).  Set (a),
+ * the written rows: d_all_offsets [T + 1], d_all_corners [n, 8] int32, class, difficult, src (row of d_boxes).  Set (b), the
+ * kept rows as dafne_assign_targets_hip reads them: d_kept_offsets [T + 1], corners f32 [n, 8] = (float)(coordinate * ratio)
+ * (the product in f64), sort_quadrilateral applied when `sort`, hull box, area (shoelace in f64, rounded), class, src.  The
+ * row arrays must hold n_pairs rows.  d_stats9: the 7 outcome counts, written rows, kept rows.
+ */
+int dafne_scene_split_labels_hip(const int32_t* d_tiles5, const int32_t* d_pair_off, int n_tiles, const int32_t* d_obj_off,
+                                 int n_scenes, const double* d_boxes, const int32_t* d_difficult, int n_objects, int patch,
+                                 double thresh, double min_area, double min_side, int32_t* d_records, int64_t n_pairs,
+                                 void* stream);
+size_t dafne_scene_pack_tile_gt_workspace_bytes(int n_tiles);
+int dafne_scene_pack_tile_gt_hip(const int32_t* d_records, const int32_t* d_pair_off, const int32_t* d_tiles5, int n_tiles,
+                                 const int32_t* d_obj_off, const int32_t* d_class, double ratio_x, double ratio_y, int sort,
+                                 int32_t* d_all_offsets, int32_t* d_all_corners, int32_t* d_all_class, int32_t* d_all_difficult,
+                                 int32_t* d_all_src, int32_t* d_kept_offsets, float* d_kept_corners, float* d_kept_hbox,
+                                 float* d_kept_area, int32_t* d_kept_class, int32_t* d_kept_src, int32_t* d_stats9, void* d_ws,
+                                 size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

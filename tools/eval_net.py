@@ -94,8 +94,13 @@ def parse_args(argv=None):
                     help="with --scene-scales: the Pillow filter of the scaled splits")
     ap.add_argument("--val-loss", action="store_true",
                     help="with --image-dir and --label-dir: the loss values the reference logs while training (loss/cls, loss/corners, "
-                         "loss/center, loss/ctr) on a labelled split, one JSON line (OneStageDetector.validation_losses)")
+                         "loss/center, loss/ctr) on a labelled split, one JSON line (OneStageDetector.validation_losses).  With "
+                         "--scene-dir and --scene-labels: the same on whole scenes and their scene-level labelTxt, the tile ground "
+                         "truth made on the device (OneStageDetector.validation_losses_scenes; rate 1, no TTA)")
     ap.add_argument("--label-dir", default="", help="with --val-loss: DOTA-format labelTxt files, <image stem>.txt per image")
+    ap.add_argument("--tile-labels-dir", default="",
+                    help="with --val-loss --scene-dir --scene-labels: also write the tile label files of the split "
+                         "(<scene>__1__<left>___<up>.txt, as ImgSplit_multi_process.py writes them) into this directory")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides")
     return ap.parse_args(argv)
 
@@ -156,8 +161,15 @@ def scene_args_error(args):
         return "--scene-labels needs --scene-dir (it scores whole-scene detections; --dataset-name scores tile detections)"
     if args.task2 and not args.scene_dir:
         return "--task2 needs --scene-dir (the horizontal-box merge runs on whole-scene detections)"
+    if getattr(args, "tile_labels_dir", "") and not (getattr(args, "val_loss", False) and args.scene_dir):
+        return "--tile-labels-dir needs --val-loss --scene-dir --scene-labels (it writes the tile labels of the scene split)"
     if not args.scene_dir:
         return None
+    if getattr(args, "val_loss", False):
+        if not args.scene_labels:
+            return "--val-loss --scene-dir needs --scene-labels (the scenes' labelTxt directory)"
+        if args.scene_tta or args.task2 or scales != (1.0,):
+            return "--val-loss --scene-dir runs the plain split at rate 1: no --scene-tta, --task2 or --scene-scales"
     if args.num_gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return "--scene-dir runs on one GPU: sharding scenes over several GPUs is not supported"
     if args.tta or args.tta_shard_views:
@@ -253,6 +265,58 @@ def run_scenes(args):
                 print(f"{k: <18}: {v:2.4f}")
             print("results_task2.txt written to %s" % out)
     return res
+
+
+def run_val_loss_scenes(args):
+    """--val-loss --scene-dir DIR --scene-labels DIR: every image file of the directory is one scene; its labelTxt is split into
+    the ground truth of every tile on the device and OneStageDetector.validation_losses_scenes runs the tiles that keep an
+    object.  Prints the batch-size-weighted mean of each term as one JSON line ("tiles": how many tiles were run); with
+    --tile-labels-dir the tile label files of the split are written as well."""
+    import json
+    from concurrent.futures import ThreadPoolExecutor
+    import dafne_amd.modeling  # noqa: F401
+    from dafne_amd.checkpoint import load_weights
+    from dafne_amd.config import load_cfg
+    from dafne_amd.data import list_image_records
+    from dafne_amd.data.loader import read_image
+    from dafne_amd.evaluation import dota_evaluation as de
+    from dafne_amd.evaluation.scene_eval import load_scene_labels
+    from dafne_amd.registry import build_model
+    from dafne_amd.utils.host import usable_cpus
+
+    cfg = load_cfg(args.config_file, args.opts)
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_net.py needs an MI355X: the HIP path has no CPU fallback")
+    dev = torch.device("cuda", 0)
+    model = build_model(cfg)
+    if args.weights or cfg.MODEL.WEIGHTS:
+        missing, unexpected = load_weights(model, args.weights or cfg.MODEL.WEIGHTS)
+        print("loaded weights: %d missing, %d unexpected keys" % (len(missing), len(unexpected)))
+    else:
+        import bench
+        model.load_state_dict(bench.seeded_state_dict(model, args.seed))
+    model.to(dev)
+    model.invalidate()
+    records = list_image_records(args.scene_dir)
+    if not records:
+        raise SystemExit("--scene-dir %s holds no image files" % args.scene_dir)
+    workers = max(1, min(args.decode_workers, usable_cpus() - 2, len(records)))
+    with ThreadPoolExecutor(workers) as pool:
+        imgs = list(pool.map(lambda r: read_image(r["file_name"], cfg.INPUT.FORMAT), records))
+    scenes = [torch.from_numpy(a).to(dev) for a in imgs]
+    names = [r["image_id"] for r in records]
+    classnames = (list(de.CLASSNAMES_DOTA_1_0) + ["container-crane"])[:cfg.MODEL.DAFNE.NUM_CLASSES]
+    labels = load_scene_labels(args.scene_labels, names, classnames)
+    if args.tile_labels_dir:
+        from dafne_amd.scene_labels import split_scene_labels, write_tile_labels
+        gt = split_scene_labels(labels, [tuple(s.shape[:2]) for s in scenes], args.patch_size, args.overlap,
+                                min_area=cfg.INPUT.MIN_AREA, min_side=cfg.INPUT.MIN_SIDE, device=dev)
+        paths = write_tile_labels(gt, names, classnames, args.tile_labels_dir)
+        print("%d tile label files written to %s: %s" % (len(paths), args.tile_labels_dir, json.dumps(gt.stats_dict())))
+    out = model.validation_losses_scenes(scenes, labels, patch_size=args.patch_size, overlap=args.overlap, batch=args.scene_batch)
+    out.pop("tile_ids")
+    print(json.dumps(out))
+    return out
 
 
 def run_val_loss(args):
@@ -513,6 +577,8 @@ def main(argv=None):
     err = scene_args_error(args)
     if err:
         raise SystemExit("eval_net.py: " + err)
+    if args.scene_dir and args.val_loss:
+        return run_val_loss_scenes(args)
     if args.scene_dir:
         return run_scenes(args)
     if args.val_loss:
