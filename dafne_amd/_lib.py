@@ -94,6 +94,11 @@ class LossParams(ctypes.Structure):
                 ("lambda_cls", c_double), ("lambda_corners", c_double), ("lambda_center", c_double), ("lambda_ctr", c_double)]
 
 
+class LevelGrad(ctypes.Structure):
+    _fields_ = [("d_logits", c_void_p), ("d_delta", c_void_p), ("d_center", c_void_p), ("d_ctrness", c_void_p),
+                ("logits_ps", c_i32), ("delta_ps", c_i32), ("center_ps", c_i32), ("ctrness_ps", c_i32)]
+
+
 # dafne_target_params.flags / dafne_loss_params.flags (include/dafne_amd.h)
 TGT_CENTER_SAMPLE, TGT_CENTER_SAMPLE_ONLY, TGT_COMBINE_CENTER_SAMPLE, TGT_IN_BOX_CHECK, TGT_LEVEL_SIZE_FILTERING, \
     TGT_FPN_STRIDE_NORM = 1, 2, 4, 8, 16, 32
@@ -209,6 +214,9 @@ SIGNATURES = {
     "dafne_assign_targets_hip": (c_int, [ctypes.POINTER(TargetParams)] + [c_void_p] * 5 + [c_int] + [c_void_p] * 6),
     "dafne_losses_workspace_bytes": (c_size_t, [ctypes.POINTER(LossParams), ctypes.POINTER(LevelDesc)]),
     "dafne_losses_hip": (c_int, [ctypes.POINTER(LossParams), ctypes.POINTER(LevelDesc)] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "dafne_losses_backward_workspace_bytes": (c_size_t, [ctypes.POINTER(LossParams), ctypes.POINTER(LevelDesc)]),
+    "dafne_losses_backward_hip": (c_int, [ctypes.POINTER(LossParams), ctypes.POINTER(LevelDesc)] + [c_void_p] * 5 +
+                                  [c_size_t, c_void_p, ctypes.POINTER(LevelGrad), c_void_p, c_size_t, c_void_p]),
     "dafne_scene_split_labels_hip": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                              c_double, c_double, c_double, c_void_p, c_i64, c_void_p]),
     "dafne_scene_pack_tile_gt_workspace_bytes": (c_size_t, [c_int]),

@@ -1,4 +1,4 @@
-// Target assignment and loss values of DAFNeOutputs for gfx950 (forward values only, no gradients).
+// Target assignment, loss values and the losses' gradients with respect to the head outputs, of DAFNeOutputs, for gfx950.
 //
 //   assign_kernel    compute_targets_for_locations + _get_ground_truth's stride division
 //                    (dafne/modeling/dafne/dafne_outputs.py:252-503): one thread per (image, location), the image's
@@ -13,6 +13,7 @@
 //                    inputs; per-workgroup partial sums (a fixed LDS tree) go to the workspace
 //   loss_final       one workgroup adds the partial sums in index order and takes the data-dependent branches
 //                    (max(num_pos, 1), max(sum ctr, 1e-6), "weights only if their sum is > 0", num_pos == 0)
+//   loss_grad        the derivative of those values with respect to the COOKED inputs (described where it is defined)
 // No floating-point atomics anywhere: two runs give equal bits.
 //
 // Output order of both kernels (and of the reference's losses(), :527): level first, then image, then location --
@@ -235,6 +236,19 @@ __device__ __forceinline__ double sl1(double n, double beta, bool logspace) {
     return logspace ? log1p(v) : v;
 }
 
+// centerness target of a positive (compute_ctrness_targets, :79-93): the ratio in fp32 as the reference forms it, the power in
+// fp64, NaN -> 0; 1 without centerness
+__device__ __forceinline__ double ctr_target(const LossDev& D, int p) {
+    if (!(D.flags & (DAFNE_LOSS_CTR_PLAIN | DAFNE_LOSS_CTR_ORIENTED))) return 1.0;
+    const float* src = (D.flags & DAFNE_LOSS_CTR_PLAIN) ? D.tl : D.ta;
+    const float s0 = src[(size_t)p * 4 + 0], s1 = src[(size_t)p * 4 + 1], s2 = src[(size_t)p * 4 + 2], s3 = src[(size_t)p * 4 + 3];
+    const float lrmin = s2 < s0 ? s2 : s0, lrmax = s2 > s0 ? s2 : s0;
+    const float tbmin = s3 < s1 ? s3 : s1, tbmax = s3 > s1 ? s3 : s1;
+    const float r = (lrmin / lrmax) * (tbmin / tbmax);
+    const double cw = pow((double)r, D.ctr_expo);
+    return cw != cw ? 0.0 : cw;
+}
+
 __global__ void __launch_bounds__(kThreads) loss_kernel(LossDev D) {
     __shared__ double red[kThreads];
     const int tid = threadIdx.x;
@@ -284,17 +298,7 @@ __global__ void __launch_bounds__(kThreads) loss_kernel(LossDev D) {
         float t[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) t[k] = D.tc[(size_t)p * 8 + k];
-        // centerness target (compute_ctrness_targets, :79-93): the ratio in fp32 as the reference forms it, the power in fp64
-        double cw = 1.0;
-        if (D.flags & (DAFNE_LOSS_CTR_PLAIN | DAFNE_LOSS_CTR_ORIENTED)) {
-            const float* src = (D.flags & DAFNE_LOSS_CTR_PLAIN) ? D.tl : D.ta;
-            const float s0 = src[(size_t)p * 4 + 0], s1 = src[(size_t)p * 4 + 1], s2 = src[(size_t)p * 4 + 2], s3 = src[(size_t)p * 4 + 3];
-            const float lrmin = s2 < s0 ? s2 : s0, lrmax = s2 > s0 ? s2 : s0;
-            const float tbmin = s3 < s1 ? s3 : s1, tbmax = s3 > s1 ? s3 : s1;
-            const float r = (lrmin / lrmax) * (tbmin / tbmax);
-            cw = pow((double)r, D.ctr_expo);
-            if (cw != cw) cw = 0.0;
-        }
+        const double cw = ctr_target(D, p);
         ctr_f = (float)cw;
         // corners (ModulatedEightPointLoss / SmoothL1Loss)
         double l0 = 0.0, l1 = 0.0, l2 = 0.0;
@@ -442,6 +446,36 @@ size_t losses_workspace_bytes(const dafne_loss_params* prm, const dafne_level_de
     return nb ? dafne::align_up((size_t)nb * kSums * sizeof(double), 256) : 0;
 }
 
+// The level table and the scalars of LossDev, with the checks of every level: shared by losses and losses_backward.
+int fill_loss_dev(const char* who, const dafne_loss_params* prm, const dafne_level_desc* levels, const int32_t* d_label,
+                  const float* d_reg_corners, const float* d_reg_ltrb, const float* d_reg_abcd, long long Pn, LossDev& D) {
+    const bool has_center = prm->flags & DAFNE_LOSS_HAS_CENTER_REG;
+    const bool has_ctr = prm->flags & (DAFNE_LOSS_CTR_PLAIN | DAFNE_LOSS_CTR_ORIENTED);
+    D.n_levels = prm->n_levels; D.C = prm->n_classes; D.P = (int)Pn; D.flags = prm->flags;
+    int off = 0;
+    for (int l = 0; l < kMaxLv; l++) {
+        D.poff[l] = off;
+        if (l < prm->n_levels) {
+            const dafne_level_desc& s = levels[l];
+            if (!s.d_logits || !s.d_delta || (has_center && !s.d_center) || (has_ctr && !s.d_ctrness))
+                return dafne::fail(DAFNE_E_INVALID, "%s: level %d lacks an input the configuration reads", who, l);
+            if (s.logits_ps < prm->n_classes || s.delta_ps < 8 || (s.d_center && s.center_ps < 2) || (s.d_ctrness && s.ctrness_ps < 1))
+                return dafne::fail(DAFNE_E_INVALID, "%s: level %d pixel stride too small", who, l);
+            D.lv[l] = LossLv{s.d_logits, s.d_delta, s.d_center, has_ctr ? s.d_ctrness : nullptr, s.logits_ps, s.delta_ps, s.center_ps,
+                             s.ctrness_ps, s.scale};
+            off += prm->n_images * s.H * s.W;
+        } else {
+            D.lv[l] = LossLv{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0.0f};
+        }
+    }
+    D.poff[kMaxLv] = off;
+    D.alpha = prm->alpha; D.gamma = prm->gamma; D.beta = prm->beta;
+    D.ctr_expo = (double)(float)(1.0 / prm->ctr_alpha);      // torch raises an fp32 tensor to the fp32 value of 1 / alpha
+    D.label = d_label; D.tc = d_reg_corners; D.tl = d_reg_ltrb; D.ta = d_reg_abcd;
+    D.partial = nullptr; D.ctr_out = nullptr;
+    return 0;
+}
+
 int losses(const dafne_loss_params* prm, const dafne_level_desc* levels, const int32_t* d_label,
                      const float* d_reg_corners, const float* d_reg_ltrb, const float* d_reg_abcd, double* d_out6,
                      float* d_ctr_targets, void* d_ws, size_t ws_bytes, void* stream) {
@@ -457,27 +491,7 @@ int losses(const dafne_loss_params* prm, const dafne_level_desc* levels, const i
     const bool has_center = prm->flags & DAFNE_LOSS_HAS_CENTER_REG;
     const bool has_ctr = prm->flags & (DAFNE_LOSS_CTR_PLAIN | DAFNE_LOSS_CTR_ORIENTED);
     LossDev D;
-    D.n_levels = prm->n_levels; D.C = prm->n_classes; D.P = (int)Pn; D.flags = prm->flags;
-    int off = 0;
-    for (int l = 0; l < kMaxLv; l++) {
-        D.poff[l] = off;
-        if (l < prm->n_levels) {
-            const dafne_level_desc& s = levels[l];
-            if (!s.d_logits || !s.d_delta || (has_center && !s.d_center) || (has_ctr && !s.d_ctrness))
-                return dafne::fail(DAFNE_E_INVALID, "losses: level %d lacks an input the configuration reads", l);
-            if (s.logits_ps < prm->n_classes || s.delta_ps < 8 || (s.d_center && s.center_ps < 2) || (s.d_ctrness && s.ctrness_ps < 1))
-                return dafne::fail(DAFNE_E_INVALID, "losses: level %d pixel stride too small", l);
-            D.lv[l] = LossLv{s.d_logits, s.d_delta, s.d_center, has_ctr ? s.d_ctrness : nullptr, s.logits_ps, s.delta_ps, s.center_ps,
-                             s.ctrness_ps, s.scale};
-            off += prm->n_images * s.H * s.W;
-        } else {
-            D.lv[l] = LossLv{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0.0f};
-        }
-    }
-    D.poff[kMaxLv] = off;
-    D.alpha = prm->alpha; D.gamma = prm->gamma; D.beta = prm->beta;
-    D.ctr_expo = (double)(float)(1.0 / prm->ctr_alpha);      // torch raises an fp32 tensor to the fp32 value of 1 / alpha
-    D.label = d_label; D.tc = d_reg_corners; D.tl = d_reg_ltrb; D.ta = d_reg_abcd;
+    if (int rc = fill_loss_dev("losses", prm, levels, d_label, d_reg_corners, d_reg_ltrb, d_reg_abcd, Pn, D)) return rc;
     D.partial = static_cast<double*>(d_ws); D.ctr_out = d_ctr_targets;
     hipLaunchKernelGGL(loss_kernel, dim3((unsigned)nb), dim3(kThreads), 0, (hipStream_t)stream, D);
     if (int rc = dafne::check_launch("losses")) return rc;
@@ -487,10 +501,230 @@ int losses(const dafne_loss_params* prm, const dafne_level_desc* levels, const i
     return dafne::check_launch("losses (final)");
 }
 
+// ------------------------------------------------------------------------------------------------ loss gradients
+// The derivative of what loss_kernel / loss_final_kernel compute, with the conventions of the reference's autograd
+// (dafne_outputs.py:620-731, smooth_l1.py): the minimum of the modulated loss sends its gradient to the FIRST of the equal
+// shifts, sort_quadrilateral's selection sends none to the slots it leaves at zero, the centerness target is a constant.
+//   loss_grad_state_kernel   re-adds the forward's partial sums of the centerness targets and of the positives in the
+//                            forward's order (loss_final_kernel's loop), so that num_pos, the sum and "sum > 0" are the
+//                            forward's own; two doubles in the workspace, no host read
+//   loss_grad_kernel         one workgroup per kThreads positions as loss_kernel: the logits gradient flat over (position,
+//                            class), the regression / centerness gradients one thread per position, zeros at non-positives.
+// Every element has one writer and is written: no memset, no atomics, equal bits from run to run.
+struct GradLv {
+    float* logits;
+    float* delta;
+    float* center;
+    float* ctr;
+    int lps, dps, cps, tps;
+};
+
+struct GradDev {
+    LossDev D;
+    GradLv g[kMaxLv];
+    const double* state;      // [2]: num_pos, sum of the centerness targets
+    const double* grad_out;   // [4]: upstream factors of cls, corners, center, ctr
+    double lam_cls, lam_corners, lam_center, lam_ctr;
+};
+
+__global__ void __launch_bounds__(64) loss_grad_state_kernel(const double* partial, int blocks, double* state) {
+    const int tid = threadIdx.x;
+    if (tid >= 2) return;
+    const int q = tid == 0 ? 7 : 6;
+    double a = 0.0;
+    for (int b = 0; b < blocks; b++) a += partial[(size_t)b * kSums + q];
+    state[tid] = a;
+}
+
+// d/dd of sl1(|d|): sign(d) * (n / beta below beta, 1 from beta on), divided by 1 + v in log space; sign(0) = 0
+__device__ __forceinline__ double sl1_grad(double d, double beta, bool logspace) {
+    const double n = fabs(d);
+    const double sg = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
+    double v = n, dv = 1.0;
+    if (!(beta < 1e-5)) {
+        if (n < beta) { v = 0.5 * n * n / beta; dv = n / beta; }
+        else v = n - 0.5 * beta;
+    }
+    if (logspace) dv = dv / (1.0 + v);
+    return sg * dv;
+}
+
+__global__ void __launch_bounds__(kThreads) loss_grad_kernel(GradDev G) {
+    const LossDev& D = G.D;
+    const int tid = threadIdx.x;
+    const int p0 = blockIdx.x * kThreads;
+    const int npos = min(kThreads, D.P - p0);
+    const double num_pos = G.state[0], csum = G.state[1];
+    const double num_pos_avg = num_pos > 1.0 ? num_pos : 1.0;
+    const double denorm = csum > 1e-6 ? csum : 1e-6;
+    const bool weighted = csum > 0.0;
+
+    if (G.g[0].logits) {
+        const double f_cls = G.lam_cls * G.grad_out[0];
+        for (int e = tid; e < npos * D.C; e += kThreads) {
+            const int q = e / D.C, c = e - q * D.C;
+            const int p = p0 + q;
+            const int l = level_of(D, p);
+            const size_t rem = (size_t)(p - D.poff[l]);
+            const double x = (double)D.lv[l].logits[rem * D.lv[l].lps + c];
+            const double t = D.label[p] == c ? 1.0 : 0.0;
+            const double pr = 1.0 / (1.0 + exp(-x));
+            const double pt = pr * t + (1.0 - pr) * (1.0 - t);
+            const double om = 1.0 - pt;
+            double g = pow(om, D.gamma) * (pr - t);
+            if (D.gamma != 0.0) {
+                const double ce = bce_logits(x, t);
+                g = g - D.gamma * pow(om, D.gamma - 1.0) * ce * ((2.0 * t - 1.0) * pr * (1.0 - pr));
+            }
+            if (D.alpha >= 0.0) g = (D.alpha * t + (1.0 - D.alpha) * (1.0 - t)) * g;
+            G.g[l].logits[rem * G.g[l].lps + c] = (float)(g / num_pos_avg * f_cls);
+        }
+    }
+
+    if (tid >= npos) return;
+    const int p = p0 + tid;
+    const int l = level_of(D, p);
+    const LossLv& L = D.lv[l];
+    const GradLv& O = G.g[l];
+    const size_t rem = (size_t)(p - D.poff[l]);
+    float gq[8], gc0 = 0.0f, gc1 = 0.0f, gt = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) gq[k] = 0.0f;
+    if (D.label[p] != D.C && num_pos > 0.0) {
+        const bool logspace = D.flags & DAFNE_LOSS_LOGSPACE;
+        float t[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) t[k] = D.tc[(size_t)p * 8 + k];
+        const double cw = ctr_target(D, p);
+        const double w = (weighted ? cw : 1.0) / denorm;
+        if (O.delta) {
+            float q[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) q[k] = L.delta[rem * L.dps + k];
+            int src[4] = {0, 1, 2, 3};
+            if (D.flags & DAFNE_LOSS_SORT_CORNERS) dafne::sort_quad_src(q, src);
+            int sh = 0;
+            if (D.flags & DAFNE_LOSS_MODULATION) {      // loss_kernel's three sums and its choice
+                double l0 = 0.0, l1 = 0.0, l2 = 0.0;
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const double tk = (double)t[k];
+                    l0 += sl1(fabs((double)q[k] - tk), D.beta, logspace);
+                    l1 += sl1(fabs((double)q[(k + 2) & 7] - tk), D.beta, logspace);
+                    l2 += sl1(fabs((double)q[(k + 6) & 7] - tk), D.beta, logspace);
+                }
+                double lc = l0;
+                if (l1 < lc) { lc = l1; sh = 1; }
+                if (l2 < lc) { lc = l2; sh = 2; }
+            }
+            const double f = w * (G.lam_corners * G.grad_out[1]);
+            float gk[8];      // by target component k
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const float qs = sh == 0 ? q[k] : (sh == 1 ? q[(k + 2) & 7] : q[(k + 6) & 7]);
+                gk[k] = (float)(sl1_grad((double)qs - (double)t[k], D.beta, logspace) * f);
+            }
+            float gs[8];      // by sorted slot j = (k + shift) & 7
+#pragma unroll
+            for (int j = 0; j < 8; j++) gs[j] = sh == 0 ? gk[j] : (sh == 1 ? gk[(j + 6) & 7] : gk[(j + 2) & 7]);
+#pragma unroll
+            for (int c = 0; c < 4; c++) {               // back through the sort: slot j came from corner src[j]
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (src[j] == c) { gq[2 * c] = gs[2 * j]; gq[2 * c + 1] = gs[2 * j + 1]; }
+            }
+        }
+        if (O.center) {
+            const double tx = ((((double)t[0] + (double)t[2]) + (double)t[4]) + (double)t[6]) / 4.0;
+            const double ty = ((((double)t[1] + (double)t[3]) + (double)t[5]) + (double)t[7]) / 4.0;
+            const double f = w * (G.lam_center * G.grad_out[2]);
+            gc0 = (float)(sl1_grad((double)L.center[rem * L.cps] - tx, D.beta, logspace) * f);
+            gc1 = (float)(sl1_grad((double)L.center[rem * L.cps + 1] - ty, D.beta, logspace) * f);
+        }
+        if (O.ctr) {
+            const double x = (double)L.ctr[rem * L.tps];
+            gt = (float)((1.0 / (1.0 + exp(-x)) - cw) / num_pos_avg * (G.lam_ctr * G.grad_out[3]));
+        }
+    }
+    if (O.delta) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) O.delta[rem * O.dps + k] = gq[k];
+    }
+    if (O.center) { O.center[rem * O.cps] = gc0; O.center[rem * O.cps + 1] = gc1; }
+    if (O.ctr) O.ctr[rem * O.tps] = gt;
+}
+
+size_t losses_backward_workspace_bytes(const dafne_loss_params* prm, const dafne_level_desc* levels) {
+    long long P = 0;
+    return loss_blocks(prm, levels, &P) ? 256 : 0;
+}
+
+int losses_backward(const dafne_loss_params* prm, const dafne_level_desc* levels, const int32_t* d_label,
+                    const float* d_reg_corners, const float* d_reg_ltrb, const float* d_reg_abcd, const void* d_fwd_ws,
+                    size_t fwd_ws_bytes, const double* d_grad_out4, const dafne_level_grad* grads, void* d_ws, size_t ws_bytes,
+                    void* stream) {
+    long long Pn = 0;
+    const int nb = loss_blocks(prm, levels, &Pn);
+    if (!nb) return dafne::fail(DAFNE_E_INVALID, "losses_backward: bad params / level table");
+    if (!d_label || !d_reg_corners || !d_reg_ltrb || !d_reg_abcd || !d_grad_out4 || !grads)
+        return dafne::fail(DAFNE_E_INVALID, "losses_backward: null pointer");
+    if (prm->flags & ~DAFNE_LOSS_ALL_FLAGS) return dafne::fail(DAFNE_E_INVALID, "losses_backward: unknown flags 0x%x", prm->flags);
+    if ((prm->flags & DAFNE_LOSS_CTR_PLAIN) && (prm->flags & DAFNE_LOSS_CTR_ORIENTED))
+        return dafne::fail(DAFNE_E_INVALID, "losses_backward: both centerness modes");
+    if (!(prm->flags & DAFNE_LOSS_COOKED))
+        return dafne::fail(DAFNE_E_UNSUPPORTED, "losses_backward: only the DAFNE_LOSS_COOKED form has a backward (the raw head "
+                                                "outputs' Scale and center + delta chain is not differentiated)");
+    if (!d_fwd_ws || fwd_ws_bytes < losses_workspace_bytes(prm, levels))
+        return dafne::fail(DAFNE_E_WORKSPACE, "losses_backward: the forward's workspace is missing or too small");
+    if (!d_ws || ws_bytes < losses_backward_workspace_bytes(prm, levels))
+        return dafne::fail(DAFNE_E_WORKSPACE, "losses_backward: workspace too small");
+    if (!(prm->ctr_alpha > 0.0)) return dafne::fail(DAFNE_E_INVALID, "losses_backward: CENTERNESS_ALPHA %g", prm->ctr_alpha);
+    const bool has_center = prm->flags & DAFNE_LOSS_HAS_CENTER_REG;
+    const bool has_ctr = prm->flags & (DAFNE_LOSS_CTR_PLAIN | DAFNE_LOSS_CTR_ORIENTED);
+    GradDev G;
+    if (int rc = fill_loss_dev("losses_backward", prm, levels, d_label, d_reg_corners, d_reg_ltrb, d_reg_abcd, Pn, G.D)) return rc;
+    for (int l = 0; l < kMaxLv; l++) {
+        if (l >= prm->n_levels) {
+            G.g[l] = GradLv{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+            continue;
+        }
+        const dafne_level_grad& g = grads[l];
+        if ((g.d_center && !has_center) || (g.d_ctrness && !has_ctr))
+            return dafne::fail(DAFNE_E_INVALID, "losses_backward: level %d has a gradient for a term the configuration lacks", l);
+        if (!g.d_logits != !grads[0].d_logits || !g.d_delta != !grads[0].d_delta || !g.d_center != !grads[0].d_center ||
+            !g.d_ctrness != !grads[0].d_ctrness)
+            return dafne::fail(DAFNE_E_INVALID, "losses_backward: level %d leaves out another set of gradients than level 0", l);
+        if ((g.d_logits && g.logits_ps < prm->n_classes) || (g.d_delta && g.delta_ps < 8) || (g.d_center && g.center_ps < 2) ||
+            (g.d_ctrness && g.ctrness_ps < 1))
+            return dafne::fail(DAFNE_E_INVALID, "losses_backward: level %d gradient pixel stride too small", l);
+        G.g[l] = GradLv{g.d_logits, g.d_delta, g.d_center, g.d_ctrness, g.logits_ps, g.delta_ps, g.center_ps, g.ctrness_ps};
+    }
+    double* state = static_cast<double*>(d_ws);
+    G.state = state; G.grad_out = d_grad_out4;
+    G.lam_cls = prm->lambda_cls; G.lam_corners = prm->lambda_corners; G.lam_center = prm->lambda_center; G.lam_ctr = prm->lambda_ctr;
+    hipLaunchKernelGGL(loss_grad_state_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, static_cast<const double*>(d_fwd_ws), nb,
+                       state);
+    if (int rc = dafne::check_launch("losses_backward (state)")) return rc;
+    hipLaunchKernelGGL(loss_grad_kernel, dim3((unsigned)nb), dim3(kThreads), 0, (hipStream_t)stream, G);
+    return dafne::check_launch("losses_backward");
+}
+
 }  // namespace targets
 }  // namespace
 
 extern "C" {
+
+size_t dafne_losses_backward_workspace_bytes(const dafne_loss_params* prm, const dafne_level_desc* levels) {
+    return targets::losses_backward_workspace_bytes(prm, levels);
+}
+
+int dafne_losses_backward_hip(const dafne_loss_params* prm, const dafne_level_desc* levels, const int32_t* d_label,
+                              const float* d_reg_corners, const float* d_reg_ltrb, const float* d_reg_abcd, const void* d_fwd_ws,
+                              size_t fwd_ws_bytes, const double* d_grad_out4, const dafne_level_grad* grads, void* d_ws,
+                              size_t ws_bytes, void* stream) {
+    return targets::losses_backward(prm, levels, d_label, d_reg_corners, d_reg_ltrb, d_reg_abcd, d_fwd_ws, fwd_ws_bytes, d_grad_out4,
+                                    grads, d_ws, ws_bytes, stream);
+}
 
 int dafne_assign_targets_hip(const dafne_target_params* prm, const float* d_gt_corners, const float* d_gt_hbox,
                              const float* d_gt_area, const int32_t* d_gt_class, const int32_t* d_gt_offsets, int n_gt,

@@ -3,8 +3,9 @@ backed by HIP kernels: the inference half (:123-190 config, :733-925) on the pos
 the training half (:44-731) -- location-to-ground-truth assignment, centerness targets and the four loss terms -- on
 csrc/targets_kernels.h.
 
-Only gradients are out of scope: there is no backward, DAFNe.forward / OneStageDetector.forward keep raising under
-``self.training``, and the losses are values for validation (OneStageDetector.validation_losses).  One process: an
+Gradients with respect to the head outputs are built (loss_function.py: losses() on inputs that require grad returns
+losses with a grad_fn, backed by dafne_losses_backward_hip); the layers' own backward is not, so DAFNe.forward /
+OneStageDetector.forward keep raising under ``self.training``.  One process: an
 initialised process group with more than one rank raises NotImplementedError (the reference all-reduces num_pos and the
 centerness sum, :44-50, 629, 665).
 """
@@ -213,14 +214,26 @@ class DAFNeOutputs(nn.Module):
         }
 
     # ---- losses (:505-731)
+    @staticmethod
+    def _require_device(tensors):
+        if not all(t.is_cuda for t in tensors):
+            raise _lib.DafneHipError("losses: the MI355X engine has no CPU path (got CPU tensors)")
+
     def losses(self, logits_pred, corners_reg_pred, center_reg_pred, ltrb_reg_pred, ctrness_pred, locations, gt_instances,
                top_feats=None):
         """The reference's eight arguments: per-level NCHW tensors as DAFNeHead.forward returns them (``locations`` is accepted
         and ignored: the kernel regenerates them; ltrb_reg_pred / top_feats are unused there too).  -> (extras, losses):
         losses {"loss/cls", "loss/corners", "loss/center" with a center regression, "loss/ctr" with centerness} as 0-dim fp32
-        device tensors, extras {"loss_denorm", "num_pos"} likewise (plus "values_f64", the kernel's fp64 row).  No host read."""
-        if not all(t.is_cuda for t in list(logits_pred) + list(corners_reg_pred)):
-            raise _lib.DafneHipError("losses: the MI355X engine has no CPU path (got CPU tensors)")
+        device tensors, extras {"loss_denorm", "num_pos"} likewise (plus "values_f64", the kernel's fp64 row).  No host read.
+        With grad mode on and any of logits_pred / corners_reg_pred / center_reg_pred / ctrness_pred requiring grad, the four
+        losses come from loss_function.DafneLossFunction and carry a grad_fn (same values, same extras)."""
+        self._require_device(list(logits_pred) + list(corners_reg_pred))
+        heads = list(logits_pred) + list(corners_reg_pred)
+        heads += list(center_reg_pred) if self.has_center_reg else []
+        heads += list(ctrness_pred) if self.has_centerness else []
+        if torch.is_grad_enabled() and any(t.requires_grad for t in heads):
+            from .loss_function import losses_with_grad
+            return losses_with_grad(self, logits_pred, corners_reg_pred, center_reg_pred, ctrness_pred, gt_instances)
 
         def nhwc(t):
             return t.detach().float().permute(0, 2, 3, 1).contiguous()
@@ -232,9 +245,10 @@ class DAFNeOutputs(nn.Module):
         tg = self.assign_targets([(lv.H, lv.W) for lv in levels], gt_instances, levels[0].logits.device)
         return self.dafne_losses_packed(levels, tg, cooked=True)
 
-    def dafne_losses_packed(self, levels, targets, cooked=False, want_ctr_targets=False):
+    def dafne_losses_packed(self, levels, targets, cooked=False, want_ctr_targets=False, _call=None):
         """dafne_losses (:620-731) on the head's raw per-level outputs (postprocess.LevelInput, NHWC, no copies: what
-        head_levels gives) and assign_targets' Targets.  cooked: the levels hold the finished regressions (losses())."""
+        head_levels gives) and assign_targets' Targets.  cooked: the levels hold the finished regressions (losses()).
+        _call: a dict that receives what a following dafne_losses_backward_hip needs (loss_function.py)."""
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("the loss kernel is single-process: the reference all-reduces num_pos and the centerness "
@@ -277,6 +291,8 @@ class DAFNeOutputs(nn.Module):
                                           _lib.ptr(targets.ltrb), _lib.ptr(targets.abcd), _lib.ptr(row), _lib.ptr(ctr_t),
                                           _lib.ptr(ws), nbytes, _lib.current_stream()), "dafne_losses_hip")
             r32 = row.to(torch.float32)
+        if _call is not None:
+            _call.update(prm=prm, descs=descs, ws=ws, ws_bytes=nbytes)
         losses = {"loss/cls": r32[0], "loss/corners": r32[1]}
         if self.has_center_reg:
             losses["loss/center"] = r32[2]

@@ -763,7 +763,7 @@ int dafne_scene_mark_hip(const int32_t* d_rank, const double* d_ovmax, const int
                          const int32_t* d_gt_offsets, int n_buckets, const uint8_t* d_difficult, int n_gt, double thresh,
                          uint8_t* d_tp, uint8_t* d_fp, void* d_ws, size_t ws_bytes, void* stream);
 
-/* ------------------------------------------------- target assignment and loss values (forward values only) */
+/* ------------------------------------------------- target assignment, loss values and the losses' gradients */
 /*
  * dafne_assign_targets_hip: compute_targets_for_locations plus _get_ground_truth's stride division
  * (dafne/modeling/dafne/dafne_outputs.py:252-503) for a batch.  Ground truth: the boxes of all images packed one after the
@@ -828,6 +828,37 @@ size_t dafne_losses_workspace_bytes(const dafne_loss_params* prm, const dafne_le
 int dafne_losses_hip(const dafne_loss_params* prm, const dafne_level_desc* levels, const int32_t* d_label,
                      const float* d_reg_corners, const float* d_reg_ltrb, const float* d_reg_abcd, double* d_out6,
                      float* d_ctr_targets, void* d_ws, size_t ws_bytes, void* stream);
+
+/*
+ * dafne_losses_backward_hip: the derivative of dafne_losses_hip's four terms (dafne_outputs.py:620-731, smooth_l1.py) with
+ * respect to the inputs that feed them, for the DAFNE_LOSS_COOKED form only (without it: DAFNE_E_UNSUPPORTED): logits <-
+ * loss/cls, corner regression <- loss/corners, center regression <- loss/center, centerness logits <- loss/ctr.  The
+ * conventions are those of the reference's autograd: the centerness target is a constant; the modulated minimum sends its
+ * gradient to the first of equal shifts (none, [1,2,3,0], [3,0,1,2]); sort_quadrilateral sends none to the output slots it
+ * leaves at zero (a quadrilateral without an l * r < 0 candidate: only the leftmost corner receives one); the smooth L1 has
+ * sign(0) = 0 and the linear branch from |x - y| == beta on.  Every term in fp64 from the fp32 inputs, times its lambda and its
+ * upstream factor d_grad_out4 [4] f64 (cls, corners, center, ctr; read on the device), rounded once to fp32.
+ * prm, levels, d_label, d_reg_*: as given to dafne_losses_hip.  d_fwd_ws / fwd_ws_bytes: that call's workspace, unchanged
+ * since -- its partial sums are added again in the forward's order, so num_pos, the centerness sum and the "sum > 0" decision
+ * are the forward's own, with no host read between the two calls.
+ * grads [n_levels]: where the gradients go, in the layout of the inputs (NHWC per level) with their own pixel strides.  Every
+ * element of every tensor given is written (zeros at non-positives for the three regression / centerness tensors): no memset,
+ * no atomics, one writer per element, equal bits from run to run.  A pointer that is NULL in every level leaves that gradient
+ * out; d_center / d_ctrness must be NULL when the configuration lacks the term.
+ * d_ws: dafne_losses_backward_workspace_bytes(prm, levels) bytes (0: bad parameters / level table).
+ */
+typedef struct dafne_level_grad {
+    float* d_logits;   /* [N, H, W, C] */
+    float* d_delta;    /* [N, H, W, 8] */
+    float* d_center;   /* [N, H, W, 2] */
+    float* d_ctrness;  /* [N, H, W]    */
+    int32_t logits_ps, delta_ps, center_ps, ctrness_ps;      /* pixel strides in floats (>= C, 8, 2, 1) */
+} dafne_level_grad;
+size_t dafne_losses_backward_workspace_bytes(const dafne_loss_params* prm, const dafne_level_desc* levels);
+int dafne_losses_backward_hip(const dafne_loss_params* prm, const dafne_level_desc* levels, const int32_t* d_label,
+                              const float* d_reg_corners, const float* d_reg_ltrb, const float* d_reg_abcd, const void* d_fwd_ws,
+                              size_t fwd_ws_bytes, const double* d_grad_out4, const dafne_level_grad* grads, void* d_ws,
+                              size_t ws_bytes, void* stream);
 
 /*
  * Scene labels -> the ground truth of every tile of a split scene (ImgSplit_multi_process.splitbase.savepatches at rate 1

@@ -3,9 +3,15 @@ next to a plain torch-on-GPU transcription of the reference's dense formulation 
 losses): profiles/NOTES_targets.md.
 
     python scripts/targets_bench.py [--batch 8] [--size 1024] [--boxes 100] [--iters 200] [--out FILE]
+    python scripts/targets_bench.py --backward [--iters 50] [--out FILE]
 
 Device events around `iters` back-to-back calls after a warm-up; the two assignments are compared (labels and indices equal)
 at the timed size before anything is timed.
+
+--backward: forward + backward of the losses.  The device path (dafne_losses_hip + dafne_losses_backward_hip on NHWC levels and
+assigned targets) against torch autograd on dense_losses, on the same device inputs with the same targets; the two alternate
+within one call, five times after a warm-up of each, at the workload's shape and at batch 2 x 512 x 512; medians with min - max.
+Also timed, for information: DAFNeOutputs.losses() on NCHW leaves + .backward(), which adds the assignment and the layout copies.
 """
 import argparse
 import json
@@ -86,7 +92,32 @@ def level_first(per, lv, n_levels):
     return [torch.cat([torch.cat([p[f][lv == l] for p in per]) for l in range(n_levels)]) for f in range(5)]
 
 
-def dense_losses(outs, logits, corners, center, ctr, tg):
+def sort_quadrilateral_torch(b):
+    """sort_quadrilateral in differentiable torch ops (gathers and selects), for the autograd baseline of --backward: the same
+    selection as dafne_amd.data.targets.sort_quadrilateral_np, zeros where no candidate has l * r < 0."""
+    n = b.shape[0]
+    S = b.view(n, 4, 2)
+    ar = torch.arange(n, device=b.device)
+    k1 = S[:, :, 0].argmin(1)
+    p1 = S[ar, k1]
+    j = torch.arange(3, device=b.device)[None]
+    R = S[ar[:, None], j + (j >= k1[:, None])]
+    d = R - p1[:, None]
+    cross = lambda u, v: u[..., 0] * v[..., 1] - u[..., 1] * v[..., 0]  # noqa: E731
+    c = torch.stack([cross(d[:, 0], d[:, 1]) * cross(d[:, 0], d[:, 2]), cross(d[:, 1], d[:, 0]) * cross(d[:, 1], d[:, 2]),
+                     cross(d[:, 2], d[:, 0]) * cross(d[:, 2], d[:, 1])], 1) < 0
+    found = c.any(1)[:, None]
+    i = c.int().argmax(1)
+    i2 = torch.tensor([1, 0, 0], device=b.device)[i]
+    i3 = torch.tensor([2, 2, 1], device=b.device)[i]
+    zero = torch.zeros_like(p1)
+    p3, A, B = torch.where(found, R[ar, i], zero), torch.where(found, R[ar, i2], zero), torch.where(found, R[ar, i3], zero)
+    e = p3 - p1
+    swap = (~(cross(e, A - p1) > 0) & (cross(e, B - p1) > 0))[:, None]
+    return torch.stack((p1, torch.where(swap, B, A), p3, torch.where(swap, A, B)), 1).view(n, 8)
+
+
+def dense_losses(outs, logits, corners, center, ctr, tg, sort=pp.sort_quadrilateral):
     lab, _, tc, _, ta = tg
     C = outs.num_classes
     pos = torch.nonzero(lab != C).squeeze(1)
@@ -108,7 +139,7 @@ def dense_losses(outs, logits, corners, center, ctr, tg):
     def sl1(x, y):
         n = torch.abs(x - y)
         return torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta).log1p()
-    q = pp.sort_quadrilateral(corners[pos])
+    q = sort(corners[pos])
     q4 = q.view(-1, 4, 2)
     l0 = sl1(q, tc[pos]).sum(1)
     l1 = sl1(q4[:, [1, 2, 3, 0]].reshape(-1, 8), tc[pos]).sum(1)
@@ -132,6 +163,76 @@ def timed(fn, iters, warmup=10):
     return e0.elapsed_time(e1) / iters * 1e3      # microseconds per call
 
 
+def setup(outs, n, size, boxes, dev, seed=0):
+    """Boxes on the device, NHWC head outputs, level shapes."""
+    rng = np.random.default_rng(seed)
+    C = outs.num_classes
+    shapes = [((size + s - 1) // s, (size + s - 1) // s) for s in STRIDES]
+    insts = [make_gt_instances(random_boxes(boxes, rng, size), rng.integers(0, C, boxes), (size, size)) for _ in range(n)]
+    for g in insts:                                   # the boxes live on the device, as a training loop would hold them
+        g.gt_corners, g.gt_corners_area, g.gt_classes = g.gt_corners.to(dev), g.gt_corners_area.to(dev), g.gt_classes.to(dev)
+        g.gt_boxes.tensor = g.gt_boxes.tensor.to(dev)
+    levels = []
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    for (h, w), s in zip(shapes, STRIDES):
+        rnd = lambda ch, m, sd: torch.randn(n, h, w, ch, device=dev, generator=gen) * sd + m  # noqa: E731
+        levels.append(pp.LevelInput(rnd(C, -3.0, 2.0), rnd(8, 0.0, 1.5), rnd(2, 0.0, 0.5), rnd(1, 0.0, 2.0), s, 1.0))
+    return shapes, insts, levels
+
+
+def backward_bench(outs, n, size, boxes, iters, dev):
+    from dafne_amd.modeling.dafne import loss_function as lf
+    C = outs.num_classes
+    shapes, insts, levels = setup(outs, n, size, boxes, dev)
+    tg = outs.assign_targets(shapes, insts, dev)
+    # dense_losses reads the targets the kernel assigned: the same labels, corner and abcd targets for both paths
+    dense_tg = (tg.labels.long(), None, tg.corners, None, tg.abcd)
+    flat = lambda k, ch: torch.cat([getattr(l, k).reshape(-1, ch) for l in levels])  # noqa: E731
+    leaves = [flat("logits", C), flat("delta", 8), flat("center", 2), flat("ctrness", 1)[:, 0].contiguous()]
+    leaves = [t.clone().requires_grad_(True) for t in leaves]
+    up = torch.ones(4, dtype=torch.float64, device=dev)
+
+    def device_path():
+        call = {}
+        outs.dafne_losses_packed(levels, tg, cooked=True, _call=call)
+        grads = [(torch.empty_like(lv.logits), torch.empty_like(lv.delta), torch.empty_like(lv.center), torch.empty_like(lv.ctrness))
+                 for lv in levels]
+        lf._backward_call(call, levels, tg, up, grads)
+        return grads
+
+    def dense_path():
+        for t in leaves:
+            t.grad = None
+        dense_losses(outs, leaves[0], leaves[1], leaves[2], leaves[3], dense_tg, sort=sort_quadrilateral_torch).sum().backward()
+
+    nchw = [[getattr(lv, k).permute(0, 3, 1, 2).contiguous().requires_grad_(True) for lv in levels]
+            for k in ("logits", "delta", "center", "ctrness")]
+
+    def module_path():
+        for ts in nchw:
+            for t in ts:
+                t.grad = None
+        _, ls = outs.losses(nchw[0], nchw[1], nchw[2], None, nchw[3], None, insts)
+        sum(ls.values()).backward()
+
+    # the two gradients agree (fp64 kernel against fp32 autograd: a loose comparison, the tests hold the tight one)
+    g = device_path()
+    dense_path()
+    torch.cuda.synchronize()
+    gl = torch.cat([x[0].reshape(-1, C) for x in g])
+    gc = torch.cat([x[1].reshape(-1, 8) for x in g])
+    agree = {"logits_max_abs_diff": float((gl - leaves[0].grad).abs().max()), "logits_max_abs": float(gl.abs().max()),
+             "corners_max_abs_diff": float((gc - leaves[1].grad).abs().max()), "corners_max_abs": float(gc.abs().max())}
+    t_dev, t_dense = [], []
+    for _ in range(5):
+        t_dev.append(timed(device_path, iters, warmup=5))
+        t_dense.append(timed(dense_path, max(5, iters // 4), warmup=3))
+    t_mod = timed(module_path, iters, warmup=5)
+    stat = lambda v: {"median_us": float(np.median(v)), "min_us": float(min(v)), "max_us": float(max(v))}  # noqa: E731
+    return {"batch": n, "size": size, "boxes_per_image": boxes, "positions": int(tg.P), "agreement": agree,
+            "device_fwd_bwd": stat(t_dev), "dense_torch_fwd_bwd": stat(t_dense), "losses_module_fwd_bwd_us": t_mod, "iters": iters}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -139,25 +240,25 @@ def main():
     ap.add_argument("--boxes", type=int, default=100)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--out", default="")
+    ap.add_argument("--backward", action="store_true", help="forward + backward of the losses against torch autograd")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("targets_bench.py needs an MI355X: a time from a CPU says nothing")
     dev = torch.device("cuda", 0)
     cfg = get_cfg()
     outs = DAFNeOutputs(cfg)
-    rng = np.random.default_rng(0)
+    if args.backward:
+        res = {"backward": [backward_bench(outs, args.batch, args.size, args.boxes, args.iters, dev),
+                            backward_bench(outs, 2, 512, args.boxes, args.iters, dev)]}
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     n, C = args.batch, outs.num_classes
-    shapes = [((args.size + s - 1) // s, (args.size + s - 1) // s) for s in STRIDES]
-    insts = [make_gt_instances(random_boxes(args.boxes, rng, args.size), rng.integers(0, C, args.boxes), (args.size, args.size))
-             for _ in range(n)]
-    for g in insts:                                   # the boxes live on the device, as a training loop would hold them
-        g.gt_corners, g.gt_corners_area, g.gt_classes = g.gt_corners.to(dev), g.gt_corners_area.to(dev), g.gt_classes.to(dev)
-        g.gt_boxes.tensor = g.gt_boxes.tensor.to(dev)
-    levels = []
-    gen = torch.Generator(device=dev).manual_seed(0)
-    for (h, w), s in zip(shapes, STRIDES):
-        rnd = lambda ch, m, sd: torch.randn(n, h, w, ch, device=dev, generator=gen) * sd + m  # noqa: E731
-        levels.append(pp.LevelInput(rnd(C, -3.0, 2.0), rnd(8, 0.0, 1.5), rnd(2, 0.0, 0.5), rnd(1, 0.0, 2.0), s, 1.0))
+    shapes, insts, levels = setup(outs, n, args.size, args.boxes, dev)
     tg = outs.assign_targets(shapes, insts, dev)
     # the dense formulation on the same inputs
     from dafne_amd.modeling.dafne.dafne import compute_locations
