@@ -46,6 +46,12 @@ class ViewSrc(ctypes.Structure):
                 ("win_h", c_i32), ("win_w", c_i32), ("hflip", c_i32), ("vflip", c_i32), ("reserved", c_i32)]
 
 
+class TrainView(ctypes.Structure):
+    _fields_ = [("d_src", c_void_p), ("h", c_i32), ("w", c_i32), ("layout_hwc", c_i32), ("left", c_i32), ("up", c_i32),
+                ("win_h", c_i32), ("win_w", c_i32), ("hflip", c_i32), ("vflip", c_i32), ("new_h", c_i32), ("new_w", c_i32),
+                ("rot", c_i32)]
+
+
 class ScaledTile(ctypes.Structure):
     _fields_ = [("d_scene", c_void_p), ("h", c_i32), ("w", c_i32), ("layout_hwc", c_i32), ("new_h", c_i32), ("new_w", c_i32),
                 ("left", c_i32), ("up", c_i32), ("filter", c_i32)]
@@ -222,6 +228,12 @@ SIGNATURES = {
     "dafne_scene_pack_tile_gt_workspace_bytes": (c_size_t, [c_int]),
     "dafne_scene_pack_tile_gt_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double, c_double, c_int] +
                                      [c_void_p] * 13 + [c_size_t, c_void_p]),
+    "dafne_train_views_workspace_bytes": (c_size_t, [ctypes.POINTER(TrainView), c_int]),
+    "dafne_train_views_u8_hip": (c_int, [ctypes.POINTER(TrainView), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                         c_void_p]),
+    "dafne_train_gt_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dafne_train_gt_hip": (c_int, [ctypes.POINTER(TrainView), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6 +
+                           [c_void_p, c_size_t, c_void_p]),
 }
 
 

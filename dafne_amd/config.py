@@ -135,7 +135,7 @@ def _defaults():
         VERSION=2, EXPERIMENT_NAME="dafne", OUTPUT_DIR="./output", SEED=-1,
         MODEL=model,
         INPUT=dict(FORMAT="BGR", MIN_SIZE_TEST=1024, MAX_SIZE_TEST=1024, MIN_SIZE_TRAIN=[1024],
-                   MAX_SIZE_TRAIN=1024, RESIZE_TYPE="shortest-edge",
+                   MAX_SIZE_TRAIN=1024, MIN_SIZE_TRAIN_SAMPLING="choice", RESIZE_TYPE="shortest-edge",
                    # dafne/config/defaults.py:10,26-27,121-134 (data-loader keys; kept so cfg reads never fail)
                    HFLIP_TRAIN=True, MIN_AREA=10, MIN_SIDE=2, ROTATION_AUG_ANGLES=[0.0, 90.0, 180.0, 270.0],
                    RESIZE_HEIGHT_TRAIN=0, RESIZE_WIDTH_TRAIN=0, RESIZE_HEIGHT_TEST=0, RESIZE_WIDTH_TEST=0,

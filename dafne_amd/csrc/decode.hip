@@ -782,3 +782,6 @@ int dafne_tta_candidates_hip(const dafne_tta_view* views, int n_views, int n_ima
 
 // ------------------------------------------------ scene labels -> tile ground truth (dafne_scene_split_labels_hip, dafne_scene_pack_tile_gt_hip)
 #include "scene_labels_kernels.h"
+
+// ------------------------------------------------ ground truth of training views (dafne_train_gt_hip)
+#include "train_views_kernels.h"

@@ -737,3 +737,254 @@ int dafne_scene_scaled_tiles_u8_hip(const dafne_scaled_tile* tiles, int n_tiles,
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------- training views
+// The batch the reference trains on (tools/plain_train_net.py:229-256: hflip, vflip, resize, quarter turns), cut straight
+// from scenes or tiles: view v = np.rot90(Pillow's BILINEAR resize of the FLIPPED zero-padded window, rot) in the top left
+// corner of its cap_h x cap_w slab, 0 in the rest of the slab (ImageList's padding), all written by one launch.
+// A workgroup owns a T x T tile of the OUTPUT.  Its pre-rotation rectangle R (T x T of the resized image, possibly hanging
+// over it) follows from rot; it runs the horizontal pass for the flipped-window rows the rectangle's vertical taps touch into
+// LDS, then the vertical pass, whose result it writes into an LDS copy of the output tile at the ROTATED position (byte
+// writes; the copy's pitch is T + 4 bytes = an odd number of words, so the 32 lanes of a half wave that walk down a column
+// of the copy on the odd rotations hit 32 different banks).  The tile leaves as 4-byte words in the output's row order for
+// every rot; bytes outside the view are written 0 by the same stores.  One writer per output byte, no atomics.
+namespace {
+
+struct TrainDev {
+    dafne_train_view s;
+    int tx, ty;                             // coefficient table of the x / y axis
+};
+
+// flipped-window pixel (r, x), channel ch: the flips come BEFORE the resize (the reference's augmentation order)
+__device__ __forceinline__ int train_px(const dafne_train_view& s, int r, int x, int ch) {
+    const int wr = s.vflip ? s.win_h - 1 - r : r, wx = s.hflip ? s.win_w - 1 - x : x;
+    const long long sy = (long long)s.up + wr, sx = (long long)s.left + wx;
+    if (sy >= s.h || sx >= s.w) return 0;
+    return s.layout_hwc ? s.d_src[((size_t)sy * s.w + sx) * 3 + ch] : s.d_src[((size_t)ch * s.h + sy) * s.w + sx];
+}
+
+__global__ void __launch_bounds__(256) train_views_kernel(const TrainDev* __restrict__ views, int n_views,
+                                                          const AxisDev* __restrict__ axes, const int* __restrict__ coef, int cap_h,
+                                                          int cap_w, int T, int rows_cap, uint8_t* __restrict__ out,
+                                                          int32_t* __restrict__ valid_hw) {
+    extern __shared__ uint8_t tmp[];         // [3][rows_cap][T], then the output tile [3][T][T + 4]
+    const int pitch = T + 4;
+    uint8_t* obuf = tmp + (size_t)3 * rows_cap * T;
+    const int tid = threadIdx.x;
+    const int ox0 = blockIdx.x * T, oy0 = blockIdx.y * T;
+    const int tw = min(T, cap_w - ox0), th = min(T, cap_h - oy0);           // the block's share of the slab (tw % 4 == 0)
+    for (int v = blockIdx.z; v < n_views; v += gridDim.z) {
+        const TrainDev vd = views[v];
+        const dafne_train_view& s = vd.s;
+        const int H = s.new_h, W = s.new_w, rot = s.rot;
+        if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
+            valid_hw[2 * v] = (rot & 1) ? W : H;
+            valid_hw[2 * v + 1] = (rot & 1) ? H : W;
+        }
+        // the tile's rectangle of the resized image: rows ry0 + [0, T), columns rx0 + [0, T)
+        //   rot 1: out[i][j] = R[j][W - 1 - i]   rot 2: R[H - 1 - i][W - 1 - j]   rot 3: R[H - 1 - j][i]      (np.rot90)
+        const int ry0 = rot == 0 ? oy0 : rot == 1 ? ox0 : rot == 2 ? H - oy0 - T : H - ox0 - T;
+        const int rx0 = rot == 0 ? ox0 : rot == 1 ? W - oy0 - T : rot == 2 ? W - ox0 - T : oy0;
+        const int ya = max(0, -ry0), yb = min(T, H - ry0), xa = max(0, -rx0), xb = min(T, W - rx0);
+        const bool any = ya < yb && xa < xb;                                 // (block-uniform)
+        const int* cx = coef + axes[vd.tx].off;
+        const int* cy = coef + axes[vd.ty].off;
+        int flo = 0;
+        if (any) {
+            // flipped-window rows of the rectangle's vertical taps: xmin is non-decreasing in the output index, and so is xmin + n
+            flo = cy[(size_t)(ry0 + ya) * kTapStride];
+            const int* clast = cy + (size_t)(ry0 + yb - 1) * kTapStride;
+            const int nrows = min(clast[0] + clast[1] - flo, rows_cap);
+            for (int e = tid; e < nrows * T; e += blockDim.x) {
+                const int r = e / T, c = e - r * T;
+                if (c < xa || c >= xb) continue;
+                const int* t = cx + (size_t)(rx0 + c) * kTapStride;
+                const int xmin = t[0], n = t[1];
+                int a0 = 1 << (kPrec - 1), a1 = a0, a2 = a0;
+                for (int x = 0; x < n; x++) {
+                    const int k = t[2 + x];
+                    a0 += train_px(s, flo + r, xmin + x, 0) * k;
+                    a1 += train_px(s, flo + r, xmin + x, 1) * k;
+                    a2 += train_px(s, flo + r, xmin + x, 2) * k;
+                }
+                tmp[(0 * rows_cap + r) * T + c] = clip8(a0);
+                tmp[(1 * rows_cap + r) * T + c] = clip8(a1);
+                tmp[(2 * rows_cap + r) * T + c] = clip8(a2);
+            }
+        }
+        __syncthreads();
+        // vertical pass over the rectangle, written at the rotated place of the output tile; 0 outside the view
+        for (int e = tid; e < T * T; e += blockDim.x) {
+            const int yl = e / T, c = e - yl * T;
+            uint8_t b0 = 0, b1 = 0, b2 = 0;
+            if (any && yl >= ya && yl < yb && c >= xa && c < xb) {
+                const int* t = cy + (size_t)(ry0 + yl) * kTapStride;
+                const int r0 = t[0] - flo, n = t[1];
+                int a0 = 1 << (kPrec - 1), a1 = a0, a2 = a0;
+                for (int y = 0; y < n; y++) {
+                    const int k = t[2 + y];
+                    const int r = r0 + y < rows_cap ? r0 + y : rows_cap - 1;     // (never clamps: rows_cap bounds the span)
+                    a0 += (int)tmp[(0 * rows_cap + r) * T + c] * k;
+                    a1 += (int)tmp[(1 * rows_cap + r) * T + c] * k;
+                    a2 += (int)tmp[(2 * rows_cap + r) * T + c] * k;
+                }
+                b0 = clip8(a0);
+                b1 = clip8(a1);
+                b2 = clip8(a2);
+            }
+            const int oyl = rot == 0 ? yl : rot == 1 ? T - 1 - c : rot == 2 ? T - 1 - yl : c;
+            const int oxl = rot == 0 ? c : rot == 1 ? yl : rot == 2 ? T - 1 - c : T - 1 - yl;
+            uint8_t* o = obuf + oyl * pitch + oxl;
+            o[0] = b0;
+            o[(size_t)T * pitch] = b1;
+            o[(size_t)2 * T * pitch] = b2;
+        }
+        __syncthreads();
+        // the tile's rows as words: byte offset ((v * 3 + ch) * cap_h + y) * cap_w + ox0 is a multiple of 4
+        const int wpr = tw / 4;
+        for (int e = tid; e < 3 * th * wpr; e += blockDim.x) {
+            const int ch = e / (th * wpr), rem = e - ch * th * wpr;
+            const int yl = rem / wpr, q = rem - yl * wpr;
+            uint32_t* dst = reinterpret_cast<uint32_t*>(out + (((size_t)v * 3 + ch) * cap_h + oy0 + yl) * cap_w + ox0);
+            dst[q] = reinterpret_cast<const uint32_t*>(obuf + ((size_t)ch * T + yl) * pitch)[q];
+        }
+        __syncthreads();
+    }
+}
+
+struct TrainPlan {
+    AxisDev* axes;          // 2 * n_views at most
+    int* tx;
+    int* ty;
+    int n_axes;
+    size_t coef_ints;
+};
+
+// the distinct (window size, new size) axes of a call; tx / ty: per view its tables.  The caller owns the arrays.
+void train_axes(const dafne_train_view* views, int n_views, TrainPlan& p) {
+    int na = 0;
+    for (int v = 0; v < n_views; v++)
+        for (int pass = 0; pass < 2; pass++) {
+            const int in = pass ? views[v].win_h : views[v].win_w, o = pass ? views[v].new_h : views[v].new_w;
+            int a = 0;
+            for (a = na - 1; a >= 0; a--)
+                if (p.axes[a].in_size == in && p.axes[a].out_size == o) break;
+            if (a < 0) {
+                a = na++;
+                p.axes[a].in_size = in;
+                p.axes[a].out_size = o;
+                p.axes[a].filter = kBilinear;
+                p.axes[a].reserved = 0;
+            }
+            (pass ? p.ty : p.tx)[v] = a;
+        }
+    size_t off = 0;
+    for (int a = 0; a < na; a++) {
+        p.axes[a].off = off;
+        off += (size_t)p.axes[a].out_size * kTapStride;
+    }
+    p.n_axes = na;
+    p.coef_ints = off;
+}
+
+bool train_view_ok(const dafne_train_view& s) {
+    return s.d_src && s.h >= 1 && s.w >= 1 && (s.layout_hwc == 0 || s.layout_hwc == 1) && s.left >= 0 && s.up >= 0 && s.win_h >= 1 &&
+           s.win_w >= 1 && (s.hflip == 0 || s.hflip == 1) && (s.vflip == 0 || s.vflip == 1) && s.new_h >= 1 && s.new_w >= 1 &&
+           s.rot >= 0 && s.rot <= 3;
+}
+
+size_t train_views_bytes(int n_views) { return dafne::align_up(sizeof(TrainDev) * (size_t)n_views, 256); }
+
+}  // namespace
+
+extern "C" {
+
+size_t dafne_train_views_workspace_bytes(const dafne_train_view* views, int n_views) {
+    if (!views || n_views < 1) return 0;
+    for (int v = 0; v < n_views; v++)
+        if (!train_view_ok(views[v])) return 0;
+    TrainPlan p;
+    p.axes = new AxisDev[2 * (size_t)n_views];
+    p.tx = new int[n_views];
+    p.ty = new int[n_views];
+    train_axes(views, n_views, p);
+    delete[] p.axes;
+    delete[] p.tx;
+    delete[] p.ty;
+    return train_views_bytes(n_views) + scaled_axes_bytes(p.n_axes) + dafne::align_up(p.coef_ints * sizeof(int), 256);
+}
+
+int dafne_train_views_u8_hip(const dafne_train_view* views, int n_views, int cap_h, int cap_w, uint8_t* d_out, int32_t* d_valid_hw,
+                             void* d_ws, size_t ws_bytes, void* stream) {
+    if (!views || !d_out || !d_valid_hw || !d_ws || n_views < 1 || cap_h < 1 || cap_w < 1)
+        return dafne::fail(DAFNE_E_INVALID, "train_views: bad args (n_views %d, cap %dx%d)", n_views, cap_h, cap_w);
+    if (cap_w % 4 || ((uintptr_t)d_out & 3))
+        return dafne::fail(DAFNE_E_UNSUPPORTED, "train_views: cap_w %d is not a multiple of 4, or the output is not 4-byte aligned", cap_w);
+    double sy_max = 0.0;
+    int in_h_max = 1, omax = 1;
+    for (int v = 0; v < n_views; v++) {
+        const dafne_train_view& s = views[v];
+        if (!train_view_ok(s))
+            return dafne::fail(DAFNE_E_INVALID, "train_views: view %d: source %dx%d layout %d window (%d, %d) %dx%d flips %d/%d -> %dx%d rot %d",
+                               v, s.h, s.w, s.layout_hwc, s.left, s.up, s.win_h, s.win_w, s.hflip, s.vflip, s.new_h, s.new_w, s.rot);
+        const int oh = (s.rot & 1) ? s.new_w : s.new_h, ow = (s.rot & 1) ? s.new_h : s.new_w;
+        if (oh > cap_h || ow > cap_w)
+            return dafne::fail(DAFNE_E_UNSUPPORTED, "train_views: view %d: %dx%d does not fit the %dx%d slab", v, oh, ow, cap_h, cap_w);
+        // the limit of dafne_resize_bilinear_u8_hip: tap count of the widest filter, 2 * ceil(support) + 1
+        const double sx = (double)s.win_w / s.new_w, sy = (double)s.win_h / s.new_h;
+        if ((sx > 1 ? sx : 1) * 2 + 2 > kMaxTaps || (sy > 1 ? sy : 1) * 2 + 2 > kMaxTaps)
+            return dafne::fail(DAFNE_E_UNSUPPORTED, "train_views: view %d: downscale factor above %d", v, kMaxTaps / 2 - 1);
+        if (sy > sy_max) sy_max = sy;
+        if (s.win_h > in_h_max) in_h_max = s.win_h;
+        if (s.new_h > omax) omax = s.new_h;
+        if (s.new_w > omax) omax = s.new_w;
+    }
+    const size_t need = dafne_train_views_workspace_bytes(views, n_views);
+    if (ws_bytes < need) return dafne::fail(DAFNE_E_WORKSPACE, "train_views: workspace %zu < %zu", ws_bytes, need);
+    TrainPlan p;
+    p.axes = new AxisDev[2 * (size_t)n_views];
+    p.tx = new int[n_views];
+    p.ty = new int[n_views];
+    train_axes(views, n_views, p);
+    // header: views + axis tables, one copy
+    const size_t vbytes = train_views_bytes(n_views), hdr = vbytes + scaled_axes_bytes(p.n_axes);
+    uint8_t* blob = new uint8_t[hdr]();
+    TrainDev* vd = reinterpret_cast<TrainDev*>(blob);
+    for (int v = 0; v < n_views; v++) {
+        vd[v].s = views[v];
+        vd[v].tx = p.tx[v];
+        vd[v].ty = p.ty[v];
+    }
+    memcpy(blob + vbytes, p.axes, sizeof(AxisDev) * (size_t)p.n_axes);
+    const int na = p.n_axes;
+    delete[] p.axes;
+    delete[] p.tx;
+    delete[] p.ty;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t ce = hipMemcpyAsync(d_ws, blob, hdr, hipMemcpyHostToDevice, st);
+    delete[] blob;
+    if (ce != hipSuccess) return dafne::fail(DAFNE_E_HIP, "train_views: hipMemcpyAsync: %s", hipGetErrorString(ce));
+    const TrainDev* d_views = (const TrainDev*)d_ws;
+    const AxisDev* d_axes = (const AxisDev*)((uint8_t*)d_ws + vbytes);
+    int* d_coef = (int*)((uint8_t*)d_ws + hdr);
+    for (int a0 = 0; a0 < na; a0 += 65535) {
+        const int n = na - a0 < 65535 ? na - a0 : 65535;
+        hipLaunchKernelGGL(views_taps_kernel, dim3((omax + 255) / 256, n), dim3(256), 0, st, d_axes + a0, n, d_coef);
+        const int rc = dafne::check_launch("train_views_taps");
+        if (rc) return rc;
+    }
+    // the tile edge: the largest of 64 .. 4 whose LDS intermediate and output tile stay within the budget
+    int T = 64, rows_cap = view_rows_cap(sy_max, T, in_h_max);
+    while (T > 4 && 3 * T * (rows_cap + T + 4) > kViewLdsBudget) {
+        T /= 2;
+        rows_cap = view_rows_cap(sy_max, T, in_h_max);
+    }
+    const size_t lds = (size_t)3 * T * (rows_cap + T + 4);
+    if (lds > 64 * 1024) return dafne::fail(DAFNE_E_UNSUPPORTED, "train_views: %d source rows per output tile", rows_cap);
+    const unsigned gz = (unsigned)(n_views < 65535 ? n_views : 65535);
+    hipLaunchKernelGGL(train_views_kernel, dim3((cap_w + T - 1) / T, (cap_h + T - 1) / T, gz), dim3(256), lds, st, d_views, n_views,
+                       d_axes, d_coef, cap_h, cap_w, T, rows_cap, d_out, d_valid_hw);
+    return dafne::check_launch("train_views");
+}
+
+}  // extern "C"

@@ -135,8 +135,9 @@ class DAFNeOutputs(nn.Module):
     # ---- target assignment (:252-503)
     def assign_targets(self, shapes, gt_instances, device):
         """shapes: (H, W) of every level; gt_instances: one Instances per image with gt_corners [G, 8], gt_boxes, gt_corners_area
-        [G], gt_classes [G] (data.targets.make_gt_instances; host or device tensors).  -> Targets.  The boxes go up in five
-        copies; nothing is read back."""
+        [G], gt_classes [G] (data.targets.make_gt_instances; host or device tensors) -- or the packed device arrays with device
+        offsets (data.train_views.PackedGT), which are handed to the kernel as they are.  -> Targets.  The boxes of Instances
+        go up in five copies; nothing is read back."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise _lib.DafneHipError("target assignment: the MI355X engine has no CPU path")
@@ -144,12 +145,26 @@ class DAFNeOutputs(nn.Module):
             raise ValueError("target assignment: %d levels, %d strides, %d sizes of interest"
                              % (len(shapes), len(self.strides), len(self.sizes_of_interest)))
         L = _lib.load()
-        n = len(gt_instances)
-        counts = [len(g.gt_classes) for g in gt_instances]
-        offsets = [0]
-        for c in counts:
-            offsets.append(offsets[-1] + c)
-        n_gt = offsets[-1]
+        packed_gt = gt_instances if hasattr(gt_instances, "offsets") and hasattr(gt_instances, "corners") else None
+        if packed_gt is not None:
+            # the packed device arrays of dafne_train_gt_hip / dafne_scene_pack_tile_gt_hip (data.train_views.PackedGT): corners
+            # [G, 8], hbox [G, 4], area [G] f32, classes [G] int32, offsets [n + 1] int32, all on the device.  Nothing is copied
+            # or read: the offsets stay where they are, G (the allocation) bounds the rows.
+            n = int(packed_gt.offsets.shape[0]) - 1
+            n_gt = int(packed_gt.corners.shape[0])
+            for t, dt in ((packed_gt.corners, torch.float32), (packed_gt.hbox, torch.float32), (packed_gt.area, torch.float32),
+                          (packed_gt.classes, torch.int32), (packed_gt.offsets, torch.int32)):
+                if t.device != dev or t.dtype != dt or not t.is_contiguous():
+                    raise ValueError("target assignment: the packed ground truth must be contiguous fp32 / int32 tensors on %s" % (dev,))
+            if packed_gt.hbox.shape[0] != n_gt or packed_gt.area.shape[0] != n_gt or packed_gt.classes.shape[0] != n_gt:
+                raise ValueError("target assignment: the packed arrays hold different row counts")
+        else:
+            n = len(gt_instances)
+            counts = [len(g.gt_classes) for g in gt_instances]
+            offsets = [0]
+            for c in counts:
+                offsets.append(offsets[-1] + c)
+            n_gt = offsets[-1]
 
         def packed(get, width, dtype):
             parts = [get(g).detach().reshape(-1, width).to(dtype) for g in gt_instances]
@@ -169,11 +184,14 @@ class DAFNeOutputs(nn.Module):
             prm.size_lo[l], prm.size_hi[l] = float(self.sizes_of_interest[l][0]), float(self.sizes_of_interest[l][1])
             prm.radius[l] = float(s * self.radius)       # get_sample_region: strides[level] * radius (:327)
         with torch.cuda.device(dev):
-            corners = packed(lambda g: g.gt_corners, 8, torch.float32)
-            hbox = packed(lambda g: g.gt_boxes.tensor, 4, torch.float32)
-            area = packed(lambda g: g.gt_corners_area, 1, torch.float32)
-            cls = packed(lambda g: g.gt_classes, 1, torch.int32)
-            off = torch.tensor(offsets, dtype=torch.int32).to(dev, non_blocking=True)
+            if packed_gt is not None:
+                corners, hbox, area, cls, off = packed_gt.corners, packed_gt.hbox, packed_gt.area, packed_gt.classes, packed_gt.offsets
+            else:
+                corners = packed(lambda g: g.gt_corners, 8, torch.float32)
+                hbox = packed(lambda g: g.gt_boxes.tensor, 4, torch.float32)
+                area = packed(lambda g: g.gt_corners_area, 1, torch.float32)
+                cls = packed(lambda g: g.gt_classes, 1, torch.int32)
+                off = torch.tensor(offsets, dtype=torch.int32).to(dev, non_blocking=True)
             _lib.check(L.dafne_assign_targets_hip(
                 ctypes.byref(prm), _lib.ptr(corners), _lib.ptr(hbox), _lib.ptr(area), _lib.ptr(cls), _lib.ptr(off), n_gt,
                 _lib.ptr(tg.labels), _lib.ptr(tg.target_inds), _lib.ptr(tg.corners), _lib.ptr(tg.ltrb), _lib.ptr(tg.abcd),

@@ -795,8 +795,18 @@ class OneStageDetector(nn.Module):
             raise NotImplementedError("training is outside the scope of the MI355X inference engine")
         if self.cfg.ENGINE.WEIGHT_DTYPE == "fp8_e4m3" and self._act_q8 is None and self.cfg.ENGINE.FP8_ACT_CALIBRATION != "off":
             raise RuntimeError("fp8 model without activation scales: call calibrate_fp8(batch) or set_fp8_act_scales(scales) first")
-        gts = [x["instances"] for x in batched_inputs]
-        batch, valid, _ = self._pack_inputs(batched_inputs)
+        if hasattr(batched_inputs, "images") and hasattr(batched_inputs, "valid_hw_host"):
+            # a data.train_views.TrainBatch: the zero-padded slab and the packed ground truth go in as they are (no copy of the
+            # pixels, no host read of the offsets); the assignment runs at the padded batch shape, as on an ImageList
+            if batched_inputs.gt is None:
+                raise ValueError("validation_losses: the TrainBatch carries no ground truth")
+            gts = batched_inputs.gt
+            batch, valid = batched_inputs.images, [tuple(v) for v in batched_inputs.valid_hw_host]
+            if batch.device != self.device:
+                raise _lib.DafneHipError("validation_losses: the TrainBatch lives on %s, the model on %s" % (batch.device, self.device))
+        else:
+            gts = [x["instances"] for x in batched_inputs]
+            batch, valid, _ = self._pack_inputs(batched_inputs)
         L = _lib.load()
         n, _, h, w = batch.shape
         hn, wn = (h + 31) // 32 * 32, (w + 31) // 32 * 32
@@ -832,6 +842,19 @@ class OneStageDetector(nn.Module):
         from .. import scene_labels
         return scene_labels.validation_losses_scenes(self, scenes, labels, patch_size=patch_size, overlap=overlap, batch=batch,
                                                      layout_hwc=layout_hwc, filter_empty=filter_empty)
+
+    def augmented_losses_scenes(self, scenes, labels, seed=0, steps=None, patch_size=1024, overlap=200, batch=8, layout_hwc=None,
+                                filter_empty=True, params_fn=None, shuffle=True):
+        """validation_losses on the AUGMENTED tiles of whole scenes -- the values the reference's training log shows, where
+        validation_losses_scenes gives the unaugmented ones.  data.train_views.scene_train_batches cuts every batch from the
+        scenes with the random flips, sizes and quarter turns of build_train_loader (tools/plain_train_net.py:229-256), drawn
+        from numpy's default_rng(seed), and transforms the ground truth on the device.  steps: batches to run (None: one pass
+        over the tiles).  -> {"loss/...": the batch-size-weighted mean, "tiles", "steps", "seed", "tile_ids", "drawn": how often
+        each flip / rot / size was drawn}.  Forward values only; raises under self.training."""
+        from ..data import train_views
+        return train_views.augmented_losses_scenes(self, scenes, labels, seed=seed, steps=steps, patch_size=patch_size, overlap=overlap,
+                                                   batch=batch, layout_hwc=layout_hwc, filter_empty=filter_empty, params_fn=params_fn,
+                                                   shuffle=shuffle)
 
     def inference(self, batched_inputs, detected_instances=None, do_postprocess=True):
         assert not self.training

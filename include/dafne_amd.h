@@ -889,6 +889,43 @@ int dafne_scene_pack_tile_gt_hip(const int32_t* d_records, const int32_t* d_pair
                                  float* d_kept_area, int32_t* d_kept_class, int32_t* d_kept_src, int32_t* d_stats9, void* d_ws,
                                  size_t ws_bytes, void* stream);
 
+/*
+ * Training views (tools/plain_train_net.py:229-256 build_train_loader: hflip, vflip, resize, quarter turns; then
+ * DAFNeDatasetMapper's ground truth), cut straight from scenes or tiles.  A view is the win_h x win_w window of its source at
+ * (left, up) (0 past the source, as dafne_view_src), flipped, THEN resized with Pillow's BILINEAR filter to new_h x new_w,
+ * then turned by rot quarter turns counter-clockwise: np.rot90(resize(flip(window)), rot), the exact permutation.
+ *   dafne_train_views_u8_hip: views is a HOST array (checked on the host, copied into d_ws on `stream`).  d_out
+ *   [n_views, 3, cap_h, cap_w] uint8, 4-byte aligned, cap_w % 4 == 0: view v fills [:oh, :ow] of its slab, (oh, ow) = (new_h,
+ *   new_w) for an even rot and (new_w, new_h) for an odd one, and every other byte of the slab is written 0 by the same launch.
+ *   d_valid_hw [n_views, 2] int32 receives (oh, ow).  cap_w % 4 != 0, a misaligned output, a view that does not fit its slab
+ *   or a downscale beyond dafne_resize_bilinear_u8_hip's tap limit -> DAFNE_E_UNSUPPORTED.  Any number of distinct (window,
+ *   new size) axes per call.  d_ws: dafne_train_views_workspace_bytes(views, n_views) bytes; 0 = invalid descriptors.
+ *   dafne_train_gt_hip: the ground truth of the same views (d_src of the descriptors is not read).  Object g of view v,
+ *   d_offsets_in[v] <= g < d_offsets_in[v + 1] (device int32 [n_views + 1]; G bounds the rows of every array), has the fp32
+ *   corners d_corners_in[g] at window scale.  In fp64, one operation at a time: x = win_w - x if hflip; y = win_h - y if vflip;
+ *   x = x * (new_w / win_w), y = y * (new_h / win_h); rot 1: (x, y) = (y, new_w - x), rot 2: (new_w - x, new_h - y), rot 3:
+ *   (new_h - y, x).  area = (float)(0.5 * |sum x_i y_(i-1) - sum y_i x_(i-1)|), the sums in index order from 0.0 (PolygonMasks.area
+ *   before the cast); the corners are rounded to fp32 once, hbox = min / max of the fp32 corners, then sort_quadrilateral is
+ *   applied when `sort`; a row is kept when hbox width > 1e-5f and height > 1e-5f (fp32; filter_empty_instances by box).  Kept rows
+ *   are packed per view in input order (count, exclusive scan over the views, ordered write; no atomics): d_corners [G, 8],
+ *   d_hbox [G, 4], d_area [G] f32, d_classes [G] int32, d_offsets_out [n_views + 1] int32, d_src [G] int32 (the input row of
+ *   every kept row) -- the arrays dafne_assign_targets_hip reads.  d_ws: dafne_train_gt_workspace_bytes(n_views, G) bytes.
+ */
+typedef struct dafne_train_view {
+    const uint8_t* d_src;
+    int32_t h, w, layout_hwc;
+    int32_t left, up, win_h, win_w;
+    int32_t hflip, vflip;
+    int32_t new_h, new_w, rot;
+} dafne_train_view;
+size_t dafne_train_views_workspace_bytes(const dafne_train_view* views, int n_views);
+int dafne_train_views_u8_hip(const dafne_train_view* views, int n_views, int cap_h, int cap_w, uint8_t* d_out, int32_t* d_valid_hw,
+                             void* d_ws, size_t ws_bytes, void* stream);
+size_t dafne_train_gt_workspace_bytes(int n_views, int G);
+int dafne_train_gt_hip(const dafne_train_view* views, int n_views, const float* d_corners_in, const int32_t* d_classes_in,
+                       const int32_t* d_offsets_in, int G, int sort, float* d_corners, float* d_hbox, float* d_area,
+                       int32_t* d_classes, int32_t* d_offsets_out, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

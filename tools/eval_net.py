@@ -101,6 +101,12 @@ def parse_args(argv=None):
     ap.add_argument("--tile-labels-dir", default="",
                     help="with --val-loss --scene-dir --scene-labels: also write the tile label files of the split "
                          "(<scene>__1__<left>___<up>.txt, as ImgSplit_multi_process.py writes them) into this directory")
+    ap.add_argument("--train-aug", action="store_true",
+                    help="with --val-loss --scene-dir --scene-labels: the loss values on AUGMENTED tiles (random flips, "
+                         "INPUT.MIN_SIZE_TRAIN sizes, INPUT.ROTATION_AUG_ANGLES quarter turns, drawn from --seed), what the reference's "
+                         "training log shows (OneStageDetector.augmented_losses_scenes); the JSON line carries the seed and how often "
+                         "each flip / turn / size was drawn")
+    ap.add_argument("--steps", type=int, default=0, help="with --train-aug: batches to run (0: one pass over the tiles)")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides")
     return ap.parse_args(argv)
 
@@ -163,6 +169,10 @@ def scene_args_error(args):
         return "--task2 needs --scene-dir (the horizontal-box merge runs on whole-scene detections)"
     if getattr(args, "tile_labels_dir", "") and not (getattr(args, "val_loss", False) and args.scene_dir):
         return "--tile-labels-dir needs --val-loss --scene-dir --scene-labels (it writes the tile labels of the scene split)"
+    if getattr(args, "train_aug", False) and not (getattr(args, "val_loss", False) and args.scene_dir):
+        return "--train-aug needs --val-loss --scene-dir --scene-labels (it augments the tiles of whole scenes)"
+    if getattr(args, "steps", 0) and not getattr(args, "train_aug", False):
+        return "--steps needs --train-aug"
     if not args.scene_dir:
         return None
     if getattr(args, "val_loss", False):
@@ -313,7 +323,11 @@ def run_val_loss_scenes(args):
                                 min_area=cfg.INPUT.MIN_AREA, min_side=cfg.INPUT.MIN_SIDE, device=dev)
         paths = write_tile_labels(gt, names, classnames, args.tile_labels_dir)
         print("%d tile label files written to %s: %s" % (len(paths), args.tile_labels_dir, json.dumps(gt.stats_dict())))
-    out = model.validation_losses_scenes(scenes, labels, patch_size=args.patch_size, overlap=args.overlap, batch=args.scene_batch)
+    if args.train_aug:
+        out = model.augmented_losses_scenes(scenes, labels, seed=args.seed, steps=args.steps or None, patch_size=args.patch_size,
+                                            overlap=args.overlap, batch=args.scene_batch)
+    else:
+        out = model.validation_losses_scenes(scenes, labels, patch_size=args.patch_size, overlap=args.overlap, batch=args.scene_batch)
     out.pop("tile_ids")
     print(json.dumps(out))
     return out
