@@ -105,6 +105,14 @@ class LevelGrad(ctypes.Structure):
                 ("logits_ps", c_i32), ("delta_ps", c_i32), ("center_ps", c_i32), ("ctrness_ps", c_i32)]
 
 
+class UncookLevel(ctypes.Structure):
+    _fields_ = [("d_g_reg", c_void_p), ("d_g_center_reg", c_void_p), ("d_g_ctrness", c_void_p), ("d_delta", c_void_p),
+                ("d_center", c_void_p), ("d_g_delta", c_void_p), ("d_g_center", c_void_p),
+                ("g_reg_ps", c_i32), ("g_center_reg_ps", c_i32), ("g_ctrness_ps", c_i32), ("delta_ps", c_i32),
+                ("center_ps", c_i32), ("g_delta_ps", c_i32), ("g_center_ps", c_i32), ("H", c_i32), ("W", c_i32),
+                ("scale", c_float)]
+
+
 # dafne_target_params.flags / dafne_loss_params.flags (include/dafne_amd.h)
 TGT_CENTER_SAMPLE, TGT_CENTER_SAMPLE_ONLY, TGT_COMBINE_CENTER_SAMPLE, TGT_IN_BOX_CHECK, TGT_LEVEL_SIZE_FILTERING, \
     TGT_FPN_STRIDE_NORM = 1, 2, 4, 8, 16, 32
@@ -167,6 +175,9 @@ SIGNATURES = {
     "dafne_conv2d_wr_splits": (c_int, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg)]),
     "dafne_conv2d_wr_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg)]),
     "dafne_conv2d_wr_hip": (c_int, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dafne_pred_wgrad_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg)]),
+    "dafne_pred_wgrad_hip": (c_int, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg), ctypes.POINTER(c_void_p), c_int,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dafne_bottleneck_body_scratch_bytes": (c_size_t, []),
     "dafne_bottleneck_body_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                           c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -223,6 +234,8 @@ SIGNATURES = {
     "dafne_losses_backward_workspace_bytes": (c_size_t, [ctypes.POINTER(LossParams), ctypes.POINTER(LevelDesc)]),
     "dafne_losses_backward_hip": (c_int, [ctypes.POINTER(LossParams), ctypes.POINTER(LevelDesc)] + [c_void_p] * 5 +
                                   [c_size_t, c_void_p, ctypes.POINTER(LevelGrad), c_void_p, c_size_t, c_void_p]),
+    "dafne_head_uncook_backward_workspace_bytes": (c_size_t, [ctypes.POINTER(UncookLevel), c_int, c_int]),
+    "dafne_head_uncook_backward_hip": (c_int, [ctypes.POINTER(UncookLevel), c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dafne_scene_split_labels_hip": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                              c_double, c_double, c_double, c_void_p, c_i64, c_void_p]),
     "dafne_scene_pack_tile_gt_workspace_bytes": (c_size_t, [c_int]),

@@ -28,6 +28,8 @@ PER_FILE = {
     "decode.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     "resize.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     "dense_ops.hip": ["-fno-slp-vectorize"],
+    # a matrix unit whose GroupNorm on load is written as scalar fp32: kept scalar (no packed fp32 at all in its listing)
+    "conv_pred_wgrad.hip": ["-fno-slp-vectorize"],
 }
 
 

@@ -785,3 +785,6 @@ int dafne_tta_candidates_hip(const dafne_tta_view* views, int n_views, int n_ima
 
 // ------------------------------------------------ ground truth of training views (dafne_train_gt_hip)
 #include "train_views_kernels.h"
+
+// ------------------------------------------------ back through the finished regressions (dafne_head_uncook_backward_hip)
+#include "pred_backward_kernels.h"

@@ -1273,8 +1273,14 @@ class HeadPlan:
                          seg_list(ins, outs, f32=True), n, gn_in=gn_in, shared_gpu=sg)
             calls.append(c)
             plan.flops += c.flops
+            # what this prediction convolution read, kept for its backward (modeling/dafne/pred_backward.py): the launch (its
+            # parameter block describes the input maps) and the tower outputs with their GroupNorm-on-load triple.  The maps
+            # stay out of the pool: nothing else may write them between the forward and the weight gradient
+            self.pred_calls[key] = c
+            self.pred_inputs[key] = (ins, gn_in)
             return outs
 
+        self.pred_calls, self.pred_inputs = {}, {}
         self.logits = pred("cls_logits", cls_t, num_classes, "logits", cls_gn)
         self.center = pred("center_pred", ctr_t, 2, "center", ctr_gn) if stacked else None
         # corners_pred (8) + ctrness (1) fused; iterative: the corners-tower parts of c0..c3_pred (8) + ctrness

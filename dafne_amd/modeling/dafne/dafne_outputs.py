@@ -4,7 +4,8 @@ the training half (:44-731) -- location-to-ground-truth assignment, centerness t
 csrc/targets_kernels.h.
 
 Gradients with respect to the head outputs are built (loss_function.py: losses() on inputs that require grad returns
-losses with a grad_fn, backed by dafne_losses_backward_hip); the layers' own backward is not, so DAFNe.forward /
+losses with a grad_fn, backed by dafne_losses_backward_hip), and so is the backward of the head's prediction layers (pred_backward.py:
+OneStageDetector.backward_prediction_layers); the backward of the towers, the FPN and the backbone is not, so DAFNe.forward /
 OneStageDetector.forward keep raising under ``self.training``.  One process: an
 initialised process group with more than one rank raises NotImplementedError (the reference all-reduces num_pos and the
 centerness sum, :44-50, 629, 665).

@@ -122,6 +122,7 @@ class OneStageDetector(nn.Module):
         self.__dict__.pop("_stream_q", None)
         self.__dict__.pop("_staging", None)          # pinned / device staging of forward_streamed's host tiles
         self.__dict__.pop("_counts_ring", None)
+        self.__dict__.pop("_last_pred_backward", None)      # (holds a plan of the weights that were just replaced)
         self._consts = {}
         if hasattr(self, "_pipe"):
             self._pipe = {}
@@ -783,7 +784,7 @@ class OneStageDetector(nn.Module):
         return [{"instances": r} for r in pp.rows_to_instances(rows, counts_h.clone(), out_hw, host_rows=rows_h)]
 
     # ------------------------------------------------------------ loss values on a labelled batch
-    def validation_losses(self, batched_inputs):
+    def validation_losses(self, batched_inputs, _slot="val"):
         """The numbers the reference logs at every training step -- loss/cls, loss/corners, loss/center, loss/ctr
         (dafne_outputs.py:620-731) -- plus "loss/total", for a labelled batch: list[{"image": uint8 CHW BGR, "instances":
         Instances with gt_corners / gt_boxes / gt_corners_area / gt_classes at the image's scale}] (the reference's training
@@ -815,7 +816,7 @@ class OneStageDetector(nn.Module):
         outs = self.proposal_generator.dafne_outputs
         with torch.cuda.device(batch.device):
             batch = batch.contiguous()
-            plan = self.plan(n, hn, wn, slot="val")       # its own buffers: a detection call in flight keeps its head outputs
+            plan = self.plan(n, hn, wn, slot=_slot)       # its own buffers: a detection call in flight keeps its head outputs
             vt = None if all(tuple(v) == (h, w) for v in valid) else self._dev_const(valid, torch.int32, (n, 2))
             _lib.check(L.dafne_preprocess_image_hip(_lib.ptr(batch), 0, n, h, w, _lib.ptr(vt), mean, std, hn, wn,
                                                     _lib.ptr(plan.stem_in), _lib.current_stream()), "dafne_preprocess_image_hip")
@@ -829,6 +830,27 @@ class OneStageDetector(nn.Module):
             losses["loss/total"] = total
         self._last_validation = {"plan": plan, "targets": tg, "extras": extras}      # (tests: what the values were computed from)
         return losses
+
+    # ------------------------------------------------------------ training the head's prediction layers (DESIGN row F11)
+    def prediction_parameters(self):
+        """The parameters backward_prediction_layers differentiates, for the optimiser: dafne_head.cls_logits.{weight,bias},
+        corners_pred.*, ctrness.* (with centerness), center_pred.* (center-to-corner) and scales.{0..4}.scale -- the module's own
+        fp32 parameters (the masters; the engine computes on bf16 copies packed from them)."""
+        from .dafne.pred_backward import prediction_parameters
+        return prediction_parameters(self)
+
+    def backward_prediction_layers(self, batched_inputs):
+        """One training step's gradients for the head's prediction layers, every launch on the device: the forward of
+        validation_losses (same argument: a batched_inputs list with "instances", or a data.train_views.TrainBatch) on a plan
+        slot of its own, target assignment, the loss backward (dafne_losses_backward_hip), back through the finished
+        regressions (dafne_head_uncook_backward_hip) and the weight gradients of the three prediction convolutions
+        (dafne_pred_wgrad_hip).  ACCUMULATES into .grad of prediction_parameters() as autograd does (created when None) and
+        returns validation_losses' dict, bit for bit.  No host read.  Eval mode (FrozenBN and per-sample GroupNorm: the
+        training forward's arithmetic; forward() keeps raising under train()); backbone, FPN and towers stay frozen and
+        get no .grad.  After optimizer.step() call invalidate(): the weights are re-packed from the parameters.  One
+        process; the iterative head and the fp8 model raise NotImplementedError."""
+        from .dafne.pred_backward import backward_prediction_layers
+        return backward_prediction_layers(self, batched_inputs)
 
     def validation_losses_scenes(self, scenes, labels, patch_size=1024, overlap=200, batch=8, layout_hwc=None, filter_empty=True):
         """validation_losses on whole scenes and their scene-level labelTxt (evaluation.scene_eval.load_scene_labels, what

@@ -327,6 +327,30 @@ size_t dafne_conv2d_wr_workspace_bytes(const dafne_conv_params* prm, const dafne
 int dafne_conv2d_wr_hip(const dafne_conv_params* prm, const dafne_conv_seg* segs, const void* d_wfrag, void* d_workspace,
                         size_t workspace_bytes, void* stream);
 /*
+ * dafne_pred_wgrad_hip (ABI 154, conv_pred_wgrad.hip): the weight and bias gradient of one of the head's prediction
+ * convolutions (cls_logits, corners_pred + ctrness, center_pred; dafne.py:318-344) -- 3x3 / stride 1 / pad 1, Cin == 256,
+ * 1 <= Cout <= 16 -- summed over every segment, image and pixel:
+ *     d_dw[co, ci, kh, kw] = sum g[s][n, y, x, co] * X[s][n, y + kh - 1, x + kw - 1, ci]        d_db[co] = sum g[s][n, y, x, co]
+ * prm / segs: the forward call's own description of its input (dafne_conv2d_nhwc_bf16_hip; flags OUT_F32, GN_INPUT and
+ * EXCLUSIVE are accepted, anything else is DAFNE_E_INVALID; d_weight, d_bias and the segments' d_out are not read and may
+ * be NULL).  X is the bf16 number the forward kernel multiplies: the stored haloed map, or with GN_INPUT GroupNorm + ReLU of
+ * it in dafne_groupnorm_relu_nhwc_bf16_hip's expression, rounded to bf16, and zero outside the image (the halo stays zero
+ * after the normalisation).  d_gout [n_segs] (a HOST array of device pointers): fp32 [N, Hout, Wout, gout_ps] per segment,
+ * channels 0 .. Cout-1 of every pixel are read (gout_ps >= Cout: a view of the leading channels of a wider buffer works,
+ * the gap is never read).  d_dw: fp32 [Cout, 256, 3, 3] (OIHW, the state-dict layout); d_db: fp32 [Cout]; every element of
+ * both is written, no memset needed.
+ * Arithmetic: v_mfma_f32_16x16x32_bf16 over the pixels with g as a hi + lo bf16 pair (|g - hi - lo| <= 2^-16 |g|) and
+ * fp32 accumulation per workgroup: |error| <= (2^-16 + n 2^-24) sum |g x| over the n summed pixels.  No atomics: each
+ * workgroup writes its partial to d_ws once, a second kernel adds the partials in workgroup order in fp64 -- equal bits from
+ * run to run.  d_ws: dafne_pred_wgrad_workspace_bytes(prm, segs) bytes (0: refused parameters, or no device).
+ * Refusals, before any launch: NULL pointers, gout_ps < Cout, n_segs outside 1..5 -> DAFNE_E_INVALID; Cin != 256, Cout
+ * outside 1..16, not 3x3 / stride 1 / pad 1, a segment above 2^20 pixels per image or 2^32 - 1 bytes of haloed input (the
+ * forward call's 32-bit offset limits) -> DAFNE_E_UNSUPPORTED; a small workspace -> DAFNE_E_WORKSPACE.
+ */
+size_t dafne_pred_wgrad_workspace_bytes(const dafne_conv_params* prm, const dafne_conv_seg* segs);
+int dafne_pred_wgrad_hip(const dafne_conv_params* prm, const dafne_conv_seg* segs, const float* const* d_gout, int gout_ps,
+                         float* d_dw, float* d_db, void* d_ws, size_t ws_bytes, void* stream);
+/*
  * fp8-weight twin (BASELINE config 5: "fp8 weights, CDNA4 fp8 MFMA conv path"; SURVEY 8(b) item 5
  * dafne_conv2d_nhwc_{bf16,fp8w}_hip).  The reference has no fp8 path: this entry DEFINES it.
  *   d_weight   OCP e4m3 bytes [Cout][Cin/64][KH][KW][64] (same K order as the bf16 layout, 1 byte per element)
@@ -859,6 +883,37 @@ int dafne_losses_backward_hip(const dafne_loss_params* prm, const dafne_level_de
                               const float* d_reg_corners, const float* d_reg_ltrb, const float* d_reg_abcd, const void* d_fwd_ws,
                               size_t fwd_ws_bytes, const double* d_grad_out4, const dafne_level_grad* grads, void* d_ws,
                               size_t ws_bytes, void* stream);
+
+/*
+ * dafne_head_uncook_backward_hip (ABI 154): dafne_losses_backward_hip differentiates with respect to the FINISHED regressions
+ * (DAFNE_LOSS_COOKED); this call carries those gradients back through DAFNeHead.forward's last step (dafne.py:394-411) to the
+ * raw outputs of the prediction convolutions and to the per-level scales:
+ *     center-to-corner  reg = (center.repeat(4) + delta) * s, center_reg = center * s        direct / offset  reg = delta * s
+ *     d_g_delta [.., 0..7] = s g_reg;  d_g_delta [.., 8] = g_ctrness (with d_g_ctrness: the fused [delta8|ctrness] layout)
+ *     d_g_center = s (sum over the four corners of g_reg + g_center_reg)
+ *     d_g_scale [l] = sum g_reg (center.repeat(4) + delta) + sum g_center_reg center      (fp64, one number per level)
+ * Per level: NHWC fp32 tensors of [n_images, H, W] pixels with their own pixel strides (floats).  d_center, d_g_center_reg and
+ * d_g_center are all given (center-to-corner) or all NULL, d_g_ctrness is given or NULL, the same way in every level.  Every
+ * value is formed in fp64 from the fp32 inputs and rounded once; d_g_scale is reduced in a fixed order without atomics (equal
+ * bits from run to run): |error| <= n 2^-53 sum |terms|.  d_ws: dafne_head_uncook_backward_workspace_bytes() bytes (0:
+ * refused).  NULL / inconsistent pointers, a pixel stride below the channels read, n_levels outside 1..8 -> DAFNE_E_INVALID;
+ * 2^31 pixels in a level -> DAFNE_E_UNSUPPORTED.  The iterative head's corner chain has no backward.
+ */
+typedef struct dafne_uncook_level {
+    const float* d_g_reg;         /* [N, H, W, 8] gradient of the finished corner regression */
+    const float* d_g_center_reg;  /* [N, H, W, 2] gradient of the finished center regression, or NULL */
+    const float* d_g_ctrness;     /* [N, H, W]    gradient of the centerness logits, or NULL */
+    const float* d_delta;         /* [N, H, W, 8] raw corners_pred output */
+    const float* d_center;        /* [N, H, W, 2] raw center_pred output, or NULL */
+    float* d_g_delta;             /* [N, H, W, 8 or 9] out */
+    float* d_g_center;            /* [N, H, W, 2] out, or NULL */
+    int32_t g_reg_ps, g_center_reg_ps, g_ctrness_ps, delta_ps, center_ps, g_delta_ps, g_center_ps;
+    int32_t H, W;
+    float scale;
+} dafne_uncook_level;
+size_t dafne_head_uncook_backward_workspace_bytes(const dafne_uncook_level* levels, int n_levels, int n_images);
+int dafne_head_uncook_backward_hip(const dafne_uncook_level* levels, int n_levels, int n_images, double* d_g_scale, void* d_ws,
+                                   size_t ws_bytes, void* stream);
 
 /*
  * Scene labels -> the ground truth of every tile of a split scene (ImgSplit_multi_process.splitbase.savepatches at rate 1
