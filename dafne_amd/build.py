@@ -30,6 +30,7 @@ PER_FILE = {
     "dense_ops.hip": ["-fno-slp-vectorize"],
     # a matrix unit whose GroupNorm on load is written as scalar fp32: kept scalar (no packed fp32 at all in its listing)
     "conv_pred_wgrad.hip": ["-fno-slp-vectorize"],
+    "conv_pred_dgrad.hip": ["-fno-slp-vectorize"],
 }
 
 

@@ -7,7 +7,8 @@ respect to the finished head outputs (loss_function.py / dafne_losses_backward_h
     uncook_backward(...)                   dafne_head_uncook_backward_hip: finished regressions -> raw delta / center / scales
     backward_prediction_layers(model, b)   what OneStageDetector.backward_prediction_layers runs
 
-The towers, the FPN and the backbone have no backward: they stay frozen.
+The last GroupNorm and bias of the complete towers are tail_backward.py's (DESIGN row F12); the rest of the towers, the FPN and the
+backbone have no backward: they stay frozen.
 """
 import ctypes
 
@@ -137,11 +138,14 @@ def _accumulate(p, g):
         p.grad.add_(g)
 
 
-def backward_prediction_layers(model, batch):
+def backward_prediction_layers(model, batch, _tail=None):
     """OneStageDetector.backward_prediction_layers: validation_losses' forward on a plan slot of its own, then target
     assignment (the forward's), the cooked loss forward + backward, the uncook kernel and three weight-gradient calls;
     accumulates into .grad of prediction_parameters(model) and returns validation_losses' dict (the same launches: the same
-    bits).  Nothing is read back to the host."""
+    bits).  Nothing is read back to the host.
+    _tail (tail_backward.backward_head_tail): called as _tail(plan, None, None) once the plan is known and before any .grad is
+    touched (it may refuse the plan), and as _tail(plan, g_logits, g_delta) after the last launch here, with the per-level loss
+    gradients with respect to the raw outputs of cls_logits and corners_pred (+ ctrness)."""
     import torch.distributed as dist
     from ... import postprocess as pp
     from .loss_function import _backward_call
@@ -159,6 +163,8 @@ def backward_prediction_layers(model, batch):
     last = model._last_validation
     plan, tg = last["plan"], last["targets"]
     hp = plan.head
+    if _tail is not None:
+        _tail(plan, None, None)
     outs = model.proposal_generator.dafne_outputs
     strides = model.proposal_generator.fpn_strides
     c2c = hp.center is not None
@@ -202,6 +208,8 @@ def backward_prediction_layers(model, batch):
         gs32 = g_scale.to(torch.float32)
         for l, sp in enumerate(head.scales):
             _accumulate(sp.scale, gs32[l:l + 1])
+        if _tail is not None:
+            _tail(plan, [g[0] for g in grads], g_delta)
     # (tests: the plan the gradients were computed on and the cooked loss forward's fp64 row, which must equal the returned
     # raw-form values bit for bit; nothing else is kept alive, and invalidate() drops it)
     model._last_pred_backward = {"plan": plan, "cooked_values_f64": cooked_extras["values_f64"]}

@@ -123,6 +123,7 @@ class OneStageDetector(nn.Module):
         self.__dict__.pop("_staging", None)          # pinned / device staging of forward_streamed's host tiles
         self.__dict__.pop("_counts_ring", None)
         self.__dict__.pop("_last_pred_backward", None)      # (holds a plan of the weights that were just replaced)
+        self.__dict__.pop("_last_head_tail", None)
         self._consts = {}
         if hasattr(self, "_pipe"):
             self._pipe = {}
@@ -851,6 +852,25 @@ class OneStageDetector(nn.Module):
         process; the iterative head and the fp8 model raise NotImplementedError."""
         from .dafne.pred_backward import backward_prediction_layers
         return backward_prediction_layers(self, batched_inputs)
+
+    # ------------------------------------------------------------ ... and each complete tower's last GroupNorm and bias (DESIGN row F12)
+    def tail_parameters(self):
+        """prediction_parameters() plus, for cls_tower and corners_tower, <tower>.9.bias, <tower>.10.weight and <tower>.10.bias:
+        what backward_head_tail differentiates.  center_tower (center-to-corner head) is excluded: its last layer also feeds
+        corners_tower.0, so its gradient is incomplete until the tower backward exists."""
+        from .dafne.tail_backward import tail_parameters
+        return tail_parameters(self)
+
+    def backward_head_tail(self, batched_inputs):
+        """backward_prediction_layers (same launches, same bits for the losses and the prediction layers' gradients), then the
+        data gradient of cls_logits and corners_pred (+ ctrness) carried back through the ReLU and the last GroupNorm of
+        cls_tower and corners_tower (dafne_pred_dgrad_gn_hip): ACCUMULATES into .grad of tail_parameters() and returns the
+        loss dict.  The gradient with respect to the raw output of <tower>.9 is kept in _last_head_tail["gx"][tower] (per level,
+        fp32 [N, H, W, 256]) until invalidate().  The weight of <tower>.9 and everything before it stay frozen.  Raises
+        NotImplementedError for the iterative head, the fp8 model, more than one rank, and with the engine switch fuse_gn_pred
+        off (the raw map is not kept there)."""
+        from .dafne.tail_backward import backward_head_tail
+        return backward_head_tail(self, batched_inputs)
 
     def validation_losses_scenes(self, scenes, labels, patch_size=1024, overlap=200, batch=8, layout_hwc=None, filter_empty=True):
         """validation_losses on whole scenes and their scene-level labelTxt (evaluation.scene_eval.load_scene_labels, what

@@ -351,6 +351,32 @@ size_t dafne_pred_wgrad_workspace_bytes(const dafne_conv_params* prm, const dafn
 int dafne_pred_wgrad_hip(const dafne_conv_params* prm, const dafne_conv_seg* segs, const float* const* d_gout, int gout_ps,
                          float* d_dw, float* d_db, void* d_ws, size_t ws_bytes, void* stream);
 /*
+ * dafne_pred_dgrad_gn_hip (ABI 155, conv_pred_dgrad.hip): the DATA gradient of one of the head's prediction convolutions, carried
+ * back through the ReLU and the GroupNorm the forward applies on load, to the raw output of the tower's last convolution.
+ * prm / segs: the forward call's own description of its input, as for dafne_pred_wgrad_hip, and GN_INPUT is REQUIRED (raw maps
+ * x, d_in_gn_stats (mean, rstd), d_in_gn_gamma, d_in_gn_beta).  d_weight: the packed bf16 weight the forward multiplied,
+ * [Cout_pad][256/64][3][3][64] (rows beyond Cout are not read).  d_gout / gout_ps: as for dafne_pred_wgrad_hip.  With groups of 8
+ * channels and m = 8 H W per (segment, image, group):
+ *     xhat = (x - mean) rstd;  a = the bf16 number the forward multiplied (dafne_groupnorm_relu_nhwc_bf16_hip's expression)
+ *     ga[y, x, ci] = sum g[y - kh + 1, x - kw + 1, co] * W[co, ci, kh, kw]  (taps outside the image: 0);   gz = ga [a > 0]
+ *     d_dgamma[c] = sum gz xhat;  d_dbeta[c] = sum gz;  gxhat = gz gamma[c];  s1 = sum_group gxhat;  s2 = sum_group gxhat xhat
+ *     d_gx[s][n, y, x, c] = rstd (gxhat - s1 / m - xhat s2 / m);   d_dbias[c] = sum d_gx
+ * (the forward's bf16 roundings are straight-through, the stored statistics are taken as the statistics of x).  d_gx [n_segs] (a
+ * HOST array of device pointers): fp32 dense [N, Hout, Wout, 256], no halo; d_dgamma, d_dbeta, d_dbias: fp32 [256] -- GroupNorm
+ * weight / bias and the bias of the convolution that wrote x.  Every element of all outputs is written.
+ * Arithmetic: v_mfma_f32_16x16x32_bf16 with exact bf16 weights and g as a hi + lo bf16 pair, fp32 accumulation; two passes over
+ * the pixels (the second recomputes ga); no atomics: per-tile and per-workgroup partials in d_ws, added in a fixed order in fp64
+ * -- equal bits from run to run.  d_ws: dafne_pred_dgrad_gn_workspace_bytes(prm, segs) bytes (0: refused parameters, or no device)
+ * = 4 * (768 * workgroups + 64 * tiles + 64 * n_segs * n_images), tiles of 4 x 32 pixels, workgroups = min(tiles, 2 * CUs).
+ * Refusals, before any launch: NULL pointers, gout_ps < Cout, n_segs outside 1..5, GN_INPUT missing or without statistics,
+ * unknown flags -> DAFNE_E_INVALID; Cin != 256, Cout outside 1..16, not 3x3 / stride 1 / pad 1, the forward call's 32-bit offset
+ * limits -> DAFNE_E_UNSUPPORTED; a small workspace -> DAFNE_E_WORKSPACE.
+ */
+size_t dafne_pred_dgrad_gn_workspace_bytes(const dafne_conv_params* prm, const dafne_conv_seg* segs);
+int dafne_pred_dgrad_gn_hip(const dafne_conv_params* prm, const dafne_conv_seg* segs, const void* d_weight,
+                            const float* const* d_gout, int gout_ps, float* const* d_gx, float* d_dgamma, float* d_dbeta,
+                            float* d_dbias, void* d_ws, size_t ws_bytes, void* stream);
+/*
  * fp8-weight twin (BASELINE config 5: "fp8 weights, CDNA4 fp8 MFMA conv path"; SURVEY 8(b) item 5
  * dafne_conv2d_nhwc_{bf16,fp8w}_hip).  The reference has no fp8 path: this entry DEFINES it.
  *   d_weight   OCP e4m3 bytes [Cout][Cin/64][KH][KW][64] (same K order as the bf16 layout, 1 byte per element)

@@ -12,6 +12,13 @@ at the timed size before anything is timed.
 assigned targets) against torch autograd on dense_losses, on the same device inputs with the same targets; the two alternate
 within one call, five times after a warm-up of each, at the workload's shape and at batch 2 x 512 x 512; medians with min - max.
 Also timed, for information: DAFNeOutputs.losses() on NCHW leaves + .backward(), which adds the assignment and the layout copies.
+
+    python scripts/targets_bench.py --tail [--iters 50] [--out FILE]
+
+--tail: dafne_pred_dgrad_gn_hip (the data gradient of a prediction convolution through the last GroupNorm of its tower) for the
+three prediction layers (Cout 15, 9, 2) at the workload's pyramid, against torch autograd on the dense formulation on the same
+device (group_norm -> relu -> conv2d in fp32 NCHW: forward + backward, and the forward alone so that the backward's share can
+be read off) and against the bytes of the kernel's two-pass scheme (2176 per pixel): profiles/NOTES_head_tail.md.
 """
 import argparse
 import json
@@ -233,6 +240,72 @@ def backward_bench(outs, n, size, boxes, iters, dev):
             "device_fwd_bwd": stat(t_dev), "dense_torch_fwd_bwd": stat(t_dense), "losses_module_fwd_bwd_us": t_mod, "iters": iters}
 
 
+def tail_bench(n, size, iters, dev):
+    import ctypes
+    import types
+    from dafne_amd import _lib, engine
+    from dafne_amd.modeling.dafne.tail_backward import pred_dgrad_gn
+    C = 256
+    shapes = [((size + s - 1) // s, (size + s - 1) // s) for s in STRIDES]
+    pixels = n * sum(h * w for h, w in shapes)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    raws, stats = [], []
+    for h, w in shapes:
+        x = (torch.randn(n, h, w, C, device=dev, generator=gen) + 0.3).to(torch.bfloat16)
+        m = torch.zeros(n, h + 2, w + 2, C, dtype=torch.bfloat16, device=dev)
+        m[:, 1:-1, 1:-1] = x
+        raws.append(m)
+        xg = x.float().reshape(n, h * w, C // 8, 8)
+        stats.append(torch.stack((xg.mean((1, 3)), 1.0 / torch.sqrt(xg.var((1, 3), unbiased=False) + 1e-5)), -1))
+    stats = torch.stack(stats).contiguous()                     # [levels, n, 32, 2]
+    gamma = torch.rand(C, device=dev, generator=gen) + 0.5
+    beta = torch.randn(C, device=dev, generator=gen) * 0.3
+    res = {"batch": n, "size": size, "pixels": pixels, "bytes_per_pixel": 2176, "iters": iters, "layers": {}}
+    for name, cout in (("cls_logits", 15), ("corners_ctrness", 9), ("center_pred", 2)):
+        W = (torch.randn(cout, C, 3, 3, generator=torch.Generator().manual_seed(cout)) * 0.05).to(torch.bfloat16).float()
+        wp = engine.pack_conv(W, None, dev)[0]
+        prm = _lib.ConvParams(n, len(raws), C, cout, 3, 3, 1, 1, 8 | 32, None, None, None, stats.data_ptr(), gamma.data_ptr(),
+                              beta.data_ptr(), None, None, 0.0)
+        segs = (_lib.ConvSeg * len(raws))()
+        for i, (m, (h, w)) in enumerate(zip(raws, shapes)):
+            segs[i] = _lib.ConvSeg(m.data_ptr(), None, None, h, w, h, w)
+        call = types.SimpleNamespace(prm=prm, segs=segs)
+        gs = [torch.randn(n, h, w, cout, device=dev, generator=gen) * 1e-3 for h, w in shapes]
+        # the dense formulation: fp32 NCHW leaves, the parameters shared by the levels
+        xs = [m[:, 1:-1, 1:-1].float().permute(0, 3, 1, 2).contiguous().requires_grad_(True) for m in raws]
+        gn = [g.permute(0, 3, 1, 2).contiguous() for g in gs]
+        ga, be, Wd = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True), W.to(dev)
+
+        def dense_forward():
+            return [torch.nn.functional.conv2d(torch.relu(torch.nn.functional.group_norm(x, 32, ga, be, 1e-5)), Wd, padding=1) for x in xs]
+
+        def dense_path():
+            for t in xs + [ga, be]:
+                t.grad = None
+            torch.autograd.backward(dense_forward(), gn)
+
+        def dense_forward_only():
+            with torch.no_grad():
+                dense_forward()
+        gx, dgamma, dbeta, _ = pred_dgrad_gn(call, wp, gs)
+        dense_path()
+        torch.cuda.synchronize()
+        agree = {"gx_max_abs_diff": max(float((a - x.grad.permute(0, 2, 3, 1)).abs().max()) for a, x in zip(gx, xs)),
+                 "gx_max_abs": max(float(a.abs().max()) for a in gx),
+                 "dgamma_max_abs_diff": float((dgamma - ga.grad).abs().max()), "dgamma_max_abs": float(dgamma.abs().max()),
+                 "dbeta_max_abs_diff": float((dbeta - be.grad).abs().max()), "dbeta_max_abs": float(dbeta.abs().max())}
+        t_dev, t_dense, t_fwd = [], [], []
+        for _ in range(5):
+            t_dev.append(timed(lambda: pred_dgrad_gn(call, wp, gs), iters, warmup=5))
+            t_dense.append(timed(dense_path, max(5, iters // 4), warmup=3))
+            t_fwd.append(timed(dense_forward_only, max(5, iters // 4), warmup=3))
+        stat = lambda v: {"median_us": float(np.median(v)), "min_us": float(min(v)), "max_us": float(max(v))}  # noqa: E731
+        d = stat(t_dev)
+        res["layers"][name] = {"cout": cout, "agreement_fp32_autograd": agree, "device": d, "dense_torch_fwd_bwd": stat(t_dense),
+                               "dense_torch_fwd": stat(t_fwd), "scheme_gbytes_per_s": pixels * 2176 / d["median_us"] / 1e3}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -241,10 +314,19 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--out", default="")
     ap.add_argument("--backward", action="store_true", help="forward + backward of the losses against torch autograd")
+    ap.add_argument("--tail", action="store_true", help="the head-tail data gradient against torch autograd and its byte count")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("targets_bench.py needs an MI355X: a time from a CPU says nothing")
     dev = torch.device("cuda", 0)
+    if args.tail:
+        line = json.dumps({"tail": tail_bench(args.batch, args.size, args.iters, dev)})
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     cfg = get_cfg()
     outs = DAFNeOutputs(cfg)
     if args.backward:
