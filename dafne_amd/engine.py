@@ -11,6 +11,7 @@ dafne/modeling/backbone/fpn.py:16-37,58-91 and dafne/modeling/dafne/dafne.py:
 350-494 (center-to-corner branch).
 """
 import ctypes
+from dataclasses import dataclass
 
 import torch
 
@@ -276,15 +277,14 @@ def pack_bneck16(w2, w3, w1):
     return torch.cat([a0.contiguous().reshape(-1), pb]).contiguous()
 
 
-def bneck_weights(P, key, w2, w3, w1):
-    """The fused res4 block's weights of P[key + "bneck"], packed on first use in the ONE form P["options"] dictates (rp_mfma16:
-    the resident-operand kernels' matrix instruction) -> (wfrag, mfma16)."""
-    f16 = P["options"].rp_mfma16
-    fkey, other = (key + "bneck16", key + "bneck") if f16 else (key + "bneck", key + "bneck16")
-    assert other not in P, "one conv_bneck form per model: %s" % other
-    if fkey not in P:
-        P[fkey] = pack_bneck16(w2, w3, w1) if f16 else pack_bneck(w2, w3, w1)
-    return P[fkey], f16
+def cached_pack(P, key, pack, other=None):
+    """P[key], packed (pack()) on first use: the lazily packed weights of a model (and the scratch buffers of a plan).  other: the
+    key the same weights would have in the other matrix-instruction form -- a model holds ONE form (P["options"].rp_mfma16), so
+    finding it is a bug."""
+    assert other is None or other not in P, "one matrix-instruction form per model: %s" % other
+    if key not in P:
+        P[key] = pack()
+    return P[key]
 
 
 def pack_conv3x3_frag(w):
@@ -317,10 +317,7 @@ def rp_weights(P, key, wgt):
     """The resident-patch weights of P[key], packed on first use in the ONE form P["options"] dictates -> (wfrag, frag16)."""
     f16 = P["options"].rp_mfma16
     fkey, other = (key + ".frag16", key + ".frag") if f16 else (key + ".frag", key + ".frag16")
-    assert other not in P, "one resident-patch form per model: %s" % other
-    if fkey not in P:
-        P[fkey] = pack_rp(wgt, P["options"])[0]
-    return P[fkey], f16
+    return cached_pack(P, fkey, lambda: pack_rp(wgt, P["options"])[0], other), f16
 
 
 def pack_conv_frag(w):
@@ -562,6 +559,87 @@ def wr_takes(k, stride, cin, cout, npx):
     return cin == 512 and cout == 256 and npx <= 40000
 
 
+# The fused bottleneck-block kernels, one entry each: what the kernel is.  DensePlan._block gives a block to the FIRST entry that
+# takes it (the order below is the order of preference: conv_bneck, the whole-block kernels, then -- behind a conv2 launch of its
+# own -- the tail + head pairs), DensePlan._emit_block launches it.  This table is where an EngineOptions switch meets its kernel.
+NEVER, MAY, MUST = 0, 1, 2
+
+
+@dataclass(frozen=True)
+class BlockKernel:
+    name: str               # launch name; + "_proj" / "_last" where proj / head is MAY and the block has a projection / no successor
+    entry: str              # library entry point
+    c: int                  # mid width (conv2 is c -> c); conv3's output, the block's, is 4c wide
+    enabled: str            # the EngineOptions property that enables it
+    key: str                # the packed weights are cached as P["resS.B." + key]
+    pack: object            # (w2, w3, w1, wsc) -> the kernel's weights; w1 / wsc are None where the block has no such piece
+    conv2: bool = False     # fuses the 3x3: reads conv1's output (otherwise conv2's, from a launch of its own)
+    proj: int = NEVER       # fuses block 0's projection shortcut: reads the block input where the others read a shortcut map
+    head: int = MUST        # fuses the next block's conv1 + ReLU
+    s2: bool = False        # stores only the even pixels (a stride-2 output)
+    scratch: str = None     # library function that returns the size of the kernel's scratch buffer
+    entry16: str = None     # a kernel with a 16x16x32 form: that form's entry point ...
+    pack16: object = None   # ... and packer; its weights are cached under key + "16" (weights() below)
+
+    def takes(self, opt, w2, w3, w1, proj, mid_c):
+        """Switch on, the block's weights have this entry's widths, and its pieces are the ones the kernel fuses.  w1: the next
+        block's conv1 weight (None: the stage's last block); proj: block 0 with a projection to fuse; mid_c: conv1's output width."""
+        c = self.c
+        return (getattr(opt, self.enabled) and tuple(w3.shape) == (4 * c, c)
+                and (not self.conv2 or (tuple(w2.shape) == (c, 9 * c) and mid_c == c))
+                and self.proj != (NEVER if proj else MUST) and self.head != (NEVER if w1 is not None else MUST)
+                and (w1 is None or tuple(w1.shape) == (c, 4 * c)))
+
+    def weights(self, P, p, w2, w3, w1, wsc):
+        """The kernel's weights for block `p` ("resS.B."), packed on first use -> (weights, is the 16x16x32 form)."""
+        # in the model's ONE matrix-instruction form (opt.rp_mfma16: 16x16x32, <= 1 bf16 ulp from the separate launches;
+        # off: 32x32x16, bit-identical to them): every plan of a model, at any batch size, runs the same one
+        f16 = self.entry16 is not None and P["options"].rp_mfma16
+        pack = self.pack16 if f16 else self.pack
+        other = None if self.entry16 is None else p + self.key + ("" if f16 else "16")
+        return cached_pack(P, p + self.key + ("16" if f16 else ""), lambda: pack(w2, w3, w1, wsc), other), f16
+
+
+def _no_head_zeros(pack):
+    # conv_bneck's no-head form still walks the conv1 section of its weights: zeros
+    return lambda w2, w3, w1, wsc: pack(w2, w3, w1 if w1 is not None else torch.zeros(256, 1024, dtype=BF16, device=w2.device))
+
+
+BLOCK_KERNELS = (
+    # res4: conv2 (3x3) + conv3 + residual + ReLU + the next block's conv1 + ReLU in ONE kernel (conv_bneck.hip): neither the
+    # 3x3's output nor conv3's is read back from HBM
+    BlockKernel("conv_bneck", "dafne_bottleneck_body_hip", 256, "bneck_on", "bneck", _no_head_zeros(pack_bneck), conv2=True, head=MAY,
+                scratch="dafne_bottleneck_body_scratch_bytes", entry16="dafne_bottleneck_body16_hip", pack16=_no_head_zeros(pack_bneck16)),
+    # res2's last block only at the pixels the next stage's stride-2 1x1 layers touch (conv_blk_narrow_s2.hip), on conv_blk_narrow's weights
+    BlockKernel("conv_blk_narrow_s2", "dafne_bottleneck_block_narrow_s2_hip", 64, "blk_narrow_on", "blk", pack_blk_narrow, conv2=True,
+                head=NEVER, s2=True, scratch="dafne_bottleneck_block_narrow_s2_scratch_bytes"),
+    # res2: the whole block -- conv2 (3x3) + conv3 + shortcut (identity / projection) + ReLU, and the next block's conv1 + ReLU
+    # when there is one -- in ONE kernel (conv_blk_narrow.hip): the 64-channel map between the 3x3 and the tail is never written or read
+    BlockKernel("conv_blk_narrow", "dafne_bottleneck_block_narrow_hip", 64, "blk_narrow_on", "blk", pack_blk_narrow, conv2=True,
+                proj=MAY, head=MAY, scratch="dafne_bottleneck_block_narrow_scratch_bytes"),
+    # res3: the whole block -- conv2 (3x3) + conv3 + shortcut + ReLU, and the next block's conv1 + ReLU when there is one -- in ONE
+    # kernel (conv_blk_mid.hip)
+    BlockKernel("conv_blk_mid", "dafne_bottleneck_block_mid_hip", 128, "blk_mid_on", "blk", lambda w2, w3, w1, wsc: pack_blk_mid(w2, w3, w1),
+                conv2=True, head=MAY, scratch="dafne_bottleneck_block_mid_scratch_bytes"),
+    # res2.0: conv3 + the projection shortcut + ReLU and the next block's conv1 + ReLU (conv_b2b_narrow.hip, PROJ)
+    BlockKernel("conv_b2b_narrow_proj", "dafne_bottleneck_proj_tail_head_narrow_hip", 64, "b2b_narrow_on", "b2b",
+                lambda w2, w3, w1, wsc: pack_b2b_narrow(w3, w1, wsc), proj=MUST),
+    # conv3 + residual + ReLU and the next block's conv1 + ReLU in one kernel (conv_b2b.hip)
+    BlockKernel("conv_b2b", "dafne_bottleneck_tail_head_hip", 256, "fuse_b2b", "b2b", lambda w2, w3, w1, wsc: pack_b2b(w3, w1)),
+    # res3: the pair with the weights streamed through LDS (conv_b2b_mid.hip)
+    BlockKernel("conv_b2b_mid", "dafne_bottleneck_tail_head_mid_hip", 128, "b2b_mid_on", "b2b", lambda w2, w3, w1, wsc: pack_b2b_mid(w3, w1)),
+    # res2: the same pair as a streaming kernel (conv_b2b_narrow.hip)
+    BlockKernel("conv_b2b_narrow", "dafne_bottleneck_tail_head_narrow_hip", 64, "b2b_narrow_on", "b2b",
+                lambda w2, w3, w1, wsc: pack_b2b_narrow(w3, w1)),
+)
+
+
+def bneck_weights(P, key, w2, w3, w1):
+    """The fused res4 block's weights of P[key + "bneck"], packed on first use in the ONE form P["options"] dictates (rp_mfma16:
+    the resident-operand kernels' matrix instruction) -> (wfrag, mfma16)."""
+    return BLOCK_KERNELS[0].weights(P, key, w2, w3, w1, None)
+
+
 class WrWorkspace:
     """Split-K workspace of a plan's dafne_conv2d_wr_hip calls (arrival tickets + fp32 partial slabs).  One per plan: its calls
     run on ONE stream, back to back, and each leaves the tickets zero.  Grown while the plan is built, allocated (zeroed) when
@@ -616,6 +694,14 @@ class FnCall:
         if rc:
             _lib.check(rc, self.name)
 
+    @classmethod
+    def of(cls, fn, name, operands, flops=0, nbytes=0):
+        """The call from ONE ordered operand list: a tensor or Act becomes a pointer argument AND is kept, an int stays an int,
+        None stays NULL -- a launch built here cannot pass a pointer it does not keep."""
+        bufs = tuple(o for o in operands if o is not None and not isinstance(o, int))
+        args = tuple(o if o is None or isinstance(o, int) else _lib.ptr(o if isinstance(o, torch.Tensor) else o.t) for o in operands)
+        return cls(fn, args, bufs, name, flops=flops, nbytes=nbytes)
+
 
 def conv_out_hw(h, w, k, stride, pad):
     return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
@@ -636,376 +722,30 @@ class DensePlan:
         # carry no F_EXCL hint.  (Until round 5 the tower layers were not paired there either: -1..-4 % in the in-phase layouts;
         # with unequal sub-batches the pairs gain +0.7 %, HeadPlan)
         self.shared_gpu = bool(shared_gpu)
-        self._build(weights, n, h, w, depth, num_classes, device, with_head, head_outputs, calib)
-
-    def _build(self, weights, n, h, w, depth, num_classes, device, with_head, head_outputs, calib):
         self.calib = calib
         self.n, self.h, self.w = n, h, w
         self.device = device
         self.calls = []
         self.flops = 0
         self.graph = None
-        L = _lib.load()
-        P = weights
-        pool = Pool(device)
-        self.pool = pool
-
-        opt = P["options"]          # (EngineOptions, fixed when the weights were packed: every plan of a model follows it)
-        shared = self.shared_gpu and not opt.shared_excl        # this plan's launches carry no F_EXCL hint
-        act_q8 = P.get("act_q8") or {}
-        wr_on = opt.conv_wr
+        self.P = weights
+        self.opt = weights["options"]   # (EngineOptions, fixed when the weights were packed: every plan of a model follows it)
+        self.pool = Pool(device)
+        self.no_excl = self.shared_gpu and not self.opt.shared_excl        # this plan's launches carry no F_EXCL hint
         self.wr_ws = WrWorkspace(device)
-        # conv3x3_c64.hip: 65 -> 49 us per launch when it has the GPU to itself, but nothing in the timed 3-stream layout (its
-        # persistent workgroups hold every CU's LDS, so the other sub-batches' kernels cannot share the chip with it): opt-in
-        use_c64 = opt.conv_c64
-        # whole-block kernels write Y = relu(conv3(T) + X) OVER X when X is dead after the block (an identity block's input, or
-        # block 0's projection output): a tile reads its own X rows and nobody else's (the halo is on the 3x3's input only), so
-        # the stores go to DRAM pages the same workgroup has just read (open rows, lines still in L2)
-        inplace_res = opt.inplace_res
-
-        def res_dead(sc_, x_, b_):
-            # the shortcut operand is not needed after the block: block 0's projection output always; an identity block's input
-            # unless it is a retained feature
-            if not inplace_res or sc_ is None:
-                return False
-            if b_ == 0:
-                return sc_ is not x_
-            return not any(sc_ is f for f in feats.values())
-
-        def conv(key, tin, k, stride, pad, flags, res=None, out=None, cout=None):
-            wgt, bias = P[key]
-            cin = tin.c
-            cout = cout or wgt.shape[0]
-            ho, wo = conv_out_hw(tin.h, tin.w, k, stride, pad)
-            o = out or pool.get(n, ho, wo, cout)
-            if (use_c64 and k == 3 and stride == 1 and pad == 1 and cin == 64 and cout == 64 and res is None
-                    and (flags & ~F_RELU) == 0 and tuple(wgt.shape) == (64, 576) and bias is not None):
-                # res2 conv2: persistent kernel with the weights in registers (conv3x3_c64.hip)
-                fl = 2 * n * ho * wo * 64 * 576
-                self.calls.append(FnCall(L.dafne_conv3x3_c64_hip,
-                                         (_lib.ptr(tin.t), _lib.ptr(wgt), _lib.ptr(bias), n, ho, wo, 1 if flags & F_RELU else 0, _lib.ptr(o.t)),
-                                         (tin, wgt, bias, o), "conv3x3_c64", flops=fl,
-                                         nbytes=2 * n * ho * wo * 64 * 2 + wgt.numel() * 2))
-                self.flops += fl
-                return o
-            q8 = P.get(key + ".fp8")
-            fp8 = None
-            if q8 is not None and k == 3 and stride == 1 and res is None and not (flags & (F_F32 | F_UP | F_RES)):
-                if calib is not None:
-                    self.calls.append(AmaxProbe(calib, key, [tin]))
-                elif key in act_q8:
-                    fp8 = (q8[1] / act_q8[key], act_q8[key])       # oscale = weight scale / in_qscale
-            c = ConvCall(q8[0] if fp8 else wgt, bias, cin, cout, k, stride, pad, flags,
-                         [(tin.t, o.t, res.t if res is not None else None, tin.h, tin.w, ho, wo)], n, fp8=fp8,
-                         shared_gpu=shared)
-            if (fp8 is None and wr_on and wr_takes(k, stride, cin, cout, WR_NOMINAL_BATCH * ho * wo) and bias is not None
-                    and L.dafne_conv2d_wr_ok(ctypes.byref(c.prm), c.segs)):
-                # small-M layer (res5, FPN top): 128 px x 256 ch tiles, weights -> registers, split-K
-                if key + ".wr" not in P:
-                    P[key + ".wr"] = pack_conv_frag(wgt)
-                w = WrCall(c, P[key + ".wr"], self.wr_ws)
-                self.calls.append(w)
-                self.flops += w.flops
-                return o
-            assert not (flags & F_RELU_INPUT), "only conv_wr rectifies its input on load (the caller checks wr_takes)"
-            if fp8 is None and k == 3 and cin == 256 and opt.conv_rp and c.kernel_id() == 6 and c.rp_ok():
-                # 256-channel 3x3 layers the patch kernel would take (FPN outputs): resident-patch kernel
-                wfrag, f16 = rp_weights(P, key, wgt)
-                c = ConvCall(wgt, bias, cin, cout, k, stride, pad, flags,
-                             [(tin.t, o.t, None, tin.h, tin.w, ho, wo)], n, wfrag=wfrag, shared_gpu=shared, frag16=f16)
-            self.calls.append(c)
-            self.flops += c.flops
-            return o
-
-        # stem: preprocess output [N, H+6, W+6, 4] -> conv7x7/s2 -> maxpool
-        self.stem_in = torch.zeros(n, h + 6, w + 6, 4, dtype=BF16, device=device)
-        wgt, bias = P["stem"]
-        x = pool.get(n, h // 4, w // 4, 64)
-        stem_flops = 2 * n * (h // 2) * (w // 2) * 64 * 7 * 7 * 3
-        stem_y1 = None            # res2.0's conv1 output when the stem kernel computed it
-        if opt.fuse_stem:
-            # conv7x7/s2 + ReLU + max-pool in one kernel: the half-resolution map never reaches HBM
-            c1 = P.get("res2.0.conv1")
-            if (opt.fuse_stem_conv1 and c1 is not None and tuple(c1[0].shape) == (64, 64)
-                    and c1[1] is not None):
-                # ... and res2.0's first convolution (1x1, 64 -> 64, ReLU) on the pooled tile while it is in LDS
-                # (stem_pool.hip CONV1): the pooled map is not read back by a launch of its own (67 MB at batch 8)
-                stem_y1 = pool.get(n, h // 4, w // 4, 64)
-                c1_flops = 2 * n * (h // 4) * (w // 4) * 64 * 64
-                fc = FnCall(L.dafne_stem_pool_conv1_hip, (_lib.ptr(self.stem_in), _lib.ptr(wgt), _lib.ptr(bias), _lib.ptr(c1[0]),
-                                                          _lib.ptr(c1[1]), n, h, w, _lib.ptr(x.t), _lib.ptr(stem_y1.t)),
-                            (self.stem_in, wgt, bias, c1[0], c1[1], x, stem_y1), "stem_pool_conv1", flops=stem_flops + c1_flops,
-                            nbytes=n * ((h + 6) * (w + 6) * 8 + (h // 4) * (w // 4) * 256))
-                self.calls.append(fc)
-                self.flops += stem_flops + c1_flops
-            else:
-                fc = FnCall(L.dafne_stem_pool_hip, (_lib.ptr(self.stem_in), _lib.ptr(wgt), _lib.ptr(bias), n, h, w, _lib.ptr(x.t)),
-                            (self.stem_in, wgt, bias, x), "stem_pool", flops=stem_flops,
-                            nbytes=n * ((h + 6) * (w + 6) * 8 + (h // 4) * (w // 4) * 128))
-                self.calls.append(fc)
-                self.flops += stem_flops
-        else:
-            stem_out = pool.get(n, h // 2, w // 2, 64)
-            c = ConvCall(wgt, bias, 4, 64, 7, 2, 3, F_RELU,
-                         [(self.stem_in, stem_out.t, None, h + 6, w + 6, h // 2, w // 2)], n, shared_gpu=shared)
-            self.calls.append(c)
-            self.flops += c.flops
-            self.calls.append(FnCall(L.dafne_maxpool3x3s2_nhwc_bf16_hip,
-                                     (_lib.ptr(stem_out.t), _lib.ptr(x.t), n, h // 2, w // 2, 64),
-                                     (stem_out, x), "maxpool"))
-            pool.put(stem_out)
-
-        feats = {}
-        fuse_b2b, fuse_narrow, fuse_mid, fuse_bneck = opt.fuse_b2b, opt.b2b_narrow_on, opt.b2b_mid_on, opt.bneck_on
-        bneck_scratch = None
-        blk_scratch = None
-        blk_mid_scratch = None
-        fuse_blk_mid, fuse_blk_narrow = opt.blk_mid_on, opt.blk_narrow_on
-        # the last block of a stage nobody but the next stage reads is computed only at the pixels the next stage's stride-2
-        # 1x1 layers touch (conv_blk_narrow_s2.hip); off: the full map (A/B runs)
-        tail_s2 = opt.res2_tail_s2
-        blk_s2_scratch = None
+        self.scratch = {}
+        self.stage_feats = {}
+        x, y1 = self._stem()
         x_compact = False         # x holds only the even pixels of the stage output: the next block 0 reads it with stride 1
         for si, nb in enumerate(STAGE_BLOCKS[depth]):
-            y1_next = stem_y1 if si == 0 else None
             for b in range(nb):
-                p = "res%d.%d." % (si + 2, b)
-                stride = 2 if (b == 0 and si > 0) else 1
-                w3, b3 = P[p + "conv3"]
-                nxt = "res%d.%d.conv1" % (si + 2, b + 1)
-                # res2.0: the projection shortcut is computed inside the fused tail (conv_b2b_narrow.hip, PROJ)
-                proj_fused = (fuse_narrow and b == 0 and stride == 1 and nb > 1 and tuple(w3.shape) == (256, 64)
-                              and tuple(P[p + "shortcut"][0].shape) == (256, 64) and tuple(P[nxt][0].shape) == (64, 256))
-                # (the whole-block kernel below takes block 0 under the same conditions: its projection is fused as well)
-                in_stride = 1 if (b == 0 and x_compact) else stride      # (the previous stage's tail has applied the stride)
-                if b == 0:
-                    sc = None if proj_fused else conv(p + "shortcut", x, 1, in_stride, 0, 0)
-                else:
-                    sc = x
-                if y1_next is not None:
-                    y1, y1_next = y1_next, None                       # computed by the previous block's fused tail
-                else:
-                    y1 = conv(p + "conv1", x, 1, in_stride, 0, F_RELU)    # STRIDE_IN_1X1
-                x_compact = False
-                w2, b2 = P[p + "conv2"]
-                q8_2 = P.get(p + "conv2.fp8")
-                bn_head = b + 1 < nb                  # the stage's last block has no next conv1: the kernel's no-head form
-                body_fused = (fuse_bneck and tuple(w3.shape) == (1024, 256) and (not bn_head or tuple(P[nxt][0].shape) == (256, 1024))
-                              and (bn_head or opt.fuse_bneck_last)
-                              and tuple(w2.shape) == (256, 2304) and y1.c == 256
-                              # an fp8 model's conv2 takes e4m3 activations on the fp8 MFMA kernel (its definition): not fused
-                              and not (q8_2 is not None and (calib is not None or (p + "conv2") in act_q8)))
-                if body_fused:
-                    # res4: conv2 (3x3) + conv3 + residual + ReLU + the next block's conv1 + ReLU in ONE kernel
-                    # (conv_bneck.hip): neither the 3x3's output nor conv3's is read back from HBM
-                    w1, b1 = P[nxt] if bn_head else (torch.zeros(256, 1024, dtype=BF16, device=w2.device), None)
-                    # in the model's ONE matrix-instruction form (opt.rp_mfma16: 16x16x32, <= 1 bf16 ulp from the separate launches;
-                    # off: 32x32x16, bit-identical to them): every plan of a model, at any batch size, runs the same one
-                    wbn, bn16 = bneck_weights(P, p, w2, w3, w1)
-                    body_fn = L.dafne_bottleneck_body16_hip if bn16 else L.dafne_bottleneck_body_hip
-                    if bneck_scratch is None:
-                        bneck_scratch = torch.empty(L.dafne_bottleneck_body_scratch_bytes(), dtype=torch.uint8, device=device)
-                    inpl = res_dead(sc, x, b)
-                    y3 = sc if inpl else pool.get(n, y1.h, y1.w, 1024)
-                    y1_next = pool.get(n, y1.h, y1.w, 256) if bn_head else None
-                    fl = 2 * n * y1.h * y1.w * (256 * 2304 + 256 * 1024 + (1024 * 256 if bn_head else 0))
-                    nb_ = n * y1.h * y1.w * (256 + 1024 + 1024 + (256 if bn_head else 0)) * 2 + (256 * 2304 + 2 * 1024 * 256) * 2
-                    self.calls.append(FnCall(body_fn,
-                                             (_lib.ptr(y1.t), _lib.ptr(sc.t), _lib.ptr(wbn), _lib.ptr(b2), _lib.ptr(b3), _lib.ptr(b1),
-                                              n, y1.h, y1.w, _lib.ptr(y3.t), _lib.ptr(y1_next.t) if bn_head else None, _lib.ptr(bneck_scratch),
-                                              bneck_scratch.numel()),
-                                             (y1, sc, wbn, b2, b3, b1, y3, y1_next, bneck_scratch),
-                                             "conv_bneck" if bn_head else "conv_bneck_last", flops=fl, nbytes=nb_))
-                    self.flops += fl
-                    pool.put(y1)
-                    if b == 0 and sc is not None and sc is not y3:
-                        pool.put(sc)
-                    if x is not y3 and not any(x is f for k, f in feats.items() if k in FPN_IN_FEATURES):
-                        pool.put(x)
-                    x = y3
-                    continue
-                if (fuse_blk_narrow and tuple(w2.shape) == (64, 576) and tuple(w3.shape) == (256, 64) and y1.c == 64 and stride == 1
-                        and (b > 0 or proj_fused) and (b + 1 >= nb or tuple(P[nxt][0].shape) == (64, 256))):
-                    # res2: the whole block -- conv2 (3x3) + conv3 + shortcut (identity / projection) + ReLU, and the next
-                    # block's conv1 + ReLU when there is one -- in ONE kernel (conv_blk_narrow.hip): the 64-channel map between
-                    # the 3x3 and the tail is never written or read
-                    head = b + 1 < nb
-                    proj = b == 0
-                    w1, b1 = P[nxt] if head else (None, None)
-                    wsc, bsc = P[p + "shortcut"] if proj else (None, None)
-                    key = p + "blk"
-                    if key not in P:
-                        P[key] = pack_blk_narrow(w2, w3, w1, wsc)
-                    if blk_scratch is None:
-                        blk_scratch = torch.empty(L.dafne_bottleneck_block_narrow_scratch_bytes(), dtype=torch.uint8, device=device)
-                    src = x if proj else sc               # projection: the block input; identity: the previous block's output
-                    nx0 = "res%d.0." % (si + 3)
-                    if (tail_s2 and calib is None and not head and not proj and si + 1 < len(STAGE_BLOCKS[depth])
-                            and "res%d" % (si + 2) not in FPN_IN_FEATURES
-                            # the only readers are the next stage's two 1x1 stride-2 layers (packed 1x1 weights: [Cout, Cin])
-                            and tuple(P[nx0 + "conv1"][0].shape)[1:] == (256,) and tuple(P[nx0 + "shortcut"][0].shape)[1:] == (256,)):
-                        if blk_s2_scratch is None:
-                            blk_s2_scratch = torch.empty(L.dafne_bottleneck_block_narrow_s2_scratch_bytes(), dtype=torch.uint8, device=device)
-                        ho, wo = (y1.h + 1) // 2, (y1.w + 1) // 2
-                        y3 = pool.get(n, ho, wo, 256)
-                        fl = 2 * n * ho * wo * (64 * 576 + 64 * 256)
-                        nb_ = n * (y1.h * y1.w * 64 + ho * wo * (256 + 256)) * 2 + (64 * 576 + 256 * 64) * 2
-                        self.calls.append(FnCall(L.dafne_bottleneck_block_narrow_s2_hip,
-                                                 (_lib.ptr(y1.t), _lib.ptr(src.t), _lib.ptr(P[key]), _lib.ptr(b2), _lib.ptr(b3), n, y1.h, y1.w,
-                                                  _lib.ptr(y3.t), _lib.ptr(blk_s2_scratch), blk_s2_scratch.numel()),
-                                                 (y1, src, P[key], b2, b3, y3, blk_s2_scratch), "conv_blk_narrow_s2", flops=fl, nbytes=nb_))
-                        self.flops += fl
-                        pool.put(y1)
-                        pool.put(x)
-                        x = y3
-                        x_compact = True
-                        continue
-                    inpl = (not proj) and res_dead(sc, x, b)
-                    y3 = sc if inpl else pool.get(n, y1.h, y1.w, 256)
-                    y1_next = pool.get(n, y1.h, y1.w, 64) if head else None
-                    px = n * y1.h * y1.w
-                    fl = 2 * px * (64 * 576 + 64 * 256 + (256 * 64 if head else 0) + (64 * 256 if proj else 0))
-                    nb_ = px * (64 + (64 if proj else 256) + 256 + (64 if head else 0)) * 2 + P[key].numel() * 2
-                    self.calls.append(FnCall(L.dafne_bottleneck_block_narrow_hip,
-                                             (_lib.ptr(y1.t), _lib.ptr(src.t), _lib.ptr(P[key]), _lib.ptr(b2), _lib.ptr(b3), _lib.ptr(bsc),
-                                              _lib.ptr(b1), n, y1.h, y1.w, _lib.ptr(y3.t), _lib.ptr(y1_next.t) if head else None,
-                                              _lib.ptr(blk_scratch), blk_scratch.numel()),
-                                             (y1, src, P[key], b2, b3, bsc, b1, y3, y1_next, blk_scratch),
-                                             "conv_blk_narrow" + ("_proj" if proj else "") + ("" if head else "_last"), flops=fl, nbytes=nb_))
-                    self.flops += fl
-                    pool.put(y1)
-                    if x is not y3 and not any(x is f for k, f in feats.items() if k in FPN_IN_FEATURES):
-                        pool.put(x)
-                    x = y3
-                    continue
-                if (fuse_blk_mid and tuple(w2.shape) == (128, 1152) and tuple(w3.shape) == (512, 128) and y1.c == 128
-                        and (b + 1 >= nb or tuple(P[nxt][0].shape) == (128, 512))):
-                    # res3: the whole block -- conv2 (3x3) + conv3 + shortcut + ReLU, and the next block's conv1 + ReLU when
-                    # there is one -- in ONE kernel (conv_blk_mid.hip)
-                    head = b + 1 < nb
-                    w1, b1 = P[nxt] if head else (None, None)
-                    key = p + "blk"
-                    if key not in P:
-                        P[key] = pack_blk_mid(w2, w3, w1)
-                    if blk_mid_scratch is None:
-                        blk_mid_scratch = torch.empty(L.dafne_bottleneck_block_mid_scratch_bytes(), dtype=torch.uint8, device=device)
-                    inpl = res_dead(sc, x, b)
-                    y3 = sc if inpl else pool.get(n, y1.h, y1.w, 512)
-                    y1_next = pool.get(n, y1.h, y1.w, 128) if head else None
-                    px = n * y1.h * y1.w
-                    fl = 2 * px * (128 * 1152 + 128 * 512 + (512 * 128 if head else 0))
-                    nb_ = px * (128 + 512 + 512 + (128 if head else 0)) * 2 + P[key].numel() * 2
-                    self.calls.append(FnCall(L.dafne_bottleneck_block_mid_hip,
-                                             (_lib.ptr(y1.t), _lib.ptr(sc.t), _lib.ptr(P[key]), _lib.ptr(b2), _lib.ptr(b3), _lib.ptr(b1),
-                                              n, y1.h, y1.w, _lib.ptr(y3.t), _lib.ptr(y1_next.t) if head else None,
-                                              _lib.ptr(blk_mid_scratch), blk_mid_scratch.numel()),
-                                             (y1, sc, P[key], b2, b3, b1, y3, y1_next, blk_mid_scratch),
-                                             "conv_blk_mid" + ("" if head else "_last"), flops=fl, nbytes=nb_))
-                    self.flops += fl
-                    pool.put(y1)
-                    if b == 0 and sc is not None and sc is not y3:
-                        pool.put(sc)
-                    if x is not y3 and not any(x is f for k, f in feats.items() if k in FPN_IN_FEATURES):
-                        pool.put(x)
-                    x = y3
-                    continue
-                y2 = conv(p + "conv2", y1, 3, 1, 1, F_RELU)
-                pool.put(y1)
-                if proj_fused:
-                    w1, b1 = P[nxt]
-                    wsc, bsc = P[p + "shortcut"]
-                    key = p + "b2b"
-                    if key not in P:
-                        P[key] = pack_b2b_narrow(w3, w1, wsc)
-                    y3 = pool.get(n, y2.h, y2.w, 256)
-                    y1_next = pool.get(n, y2.h, y2.w, 64)
-                    fl = 2 * n * y2.h * y2.w * (64 * 256 * 2 + 256 * 64)
-                    nb_ = n * y2.h * y2.w * (64 + 64 + 256 + 64) * 2 + 3 * 256 * 64 * 2
-                    self.calls.append(FnCall(L.dafne_bottleneck_proj_tail_head_narrow_hip,
-                                             (_lib.ptr(y2.t), _lib.ptr(x.t), _lib.ptr(P[key]), _lib.ptr(b3), _lib.ptr(bsc), _lib.ptr(b1),
-                                              n, y2.h, y2.w, _lib.ptr(y3.t), _lib.ptr(y1_next.t)),
-                                             (y2, x, P[key], b3, bsc, b1, y3, y1_next), "conv_b2b_narrow_proj", flops=fl, nbytes=nb_))
-                    self.flops += fl
-                elif fuse_b2b and b + 1 < nb and tuple(w3.shape) == (1024, 256) and tuple(P[nxt][0].shape) == (256, 1024):
-                    # conv3 + residual + ReLU and the next block's conv1 + ReLU in one kernel (conv_b2b.hip)
-                    w1, b1 = P[nxt]
-                    key = p + "b2b"
-                    if key not in P:
-                        P[key] = pack_b2b(w3, w1)
-                    y3 = pool.get(n, y2.h, y2.w, 1024)
-                    y1_next = pool.get(n, y2.h, y2.w, 256)
-                    fl = 2 * n * y2.h * y2.w * (256 * 1024 + 1024 * 256)
-                    nb_ = n * y2.h * y2.w * (256 + 1024 + 1024 + 256) * 2 + 2 * 1024 * 256 * 2
-                    self.calls.append(FnCall(L.dafne_bottleneck_tail_head_hip,
-                                             (_lib.ptr(y2.t), _lib.ptr(sc.t), _lib.ptr(P[key]), _lib.ptr(b3), _lib.ptr(b1),
-                                              n, y2.h, y2.w, _lib.ptr(y3.t), _lib.ptr(y1_next.t)),
-                                             (y2, sc, P[key], b3, b1, y3, y1_next), "conv_b2b", flops=fl, nbytes=nb_))
-                    self.flops += fl
-                elif fuse_mid and b + 1 < nb and tuple(w3.shape) == (512, 128) and tuple(P[nxt][0].shape) == (128, 512):
-                    # res3: the pair with the weights streamed through LDS (conv_b2b_mid.hip)
-                    w1, b1 = P[nxt]
-                    key = p + "b2b"
-                    if key not in P:
-                        P[key] = pack_b2b_mid(w3, w1)
-                    y3 = pool.get(n, y2.h, y2.w, 512)
-                    y1_next = pool.get(n, y2.h, y2.w, 128)
-                    fl = 2 * n * y2.h * y2.w * (128 * 512 + 512 * 128)
-                    nb_ = n * y2.h * y2.w * (128 + 512 + 512 + 128) * 2 + 2 * 512 * 128 * 2
-                    self.calls.append(FnCall(L.dafne_bottleneck_tail_head_mid_hip,
-                                             (_lib.ptr(y2.t), _lib.ptr(sc.t), _lib.ptr(P[key]), _lib.ptr(b3), _lib.ptr(b1),
-                                              n, y2.h, y2.w, _lib.ptr(y3.t), _lib.ptr(y1_next.t)),
-                                             (y2, sc, P[key], b3, b1, y3, y1_next), "conv_b2b_mid", flops=fl, nbytes=nb_))
-                    self.flops += fl
-                elif fuse_narrow and b + 1 < nb and tuple(w3.shape) == (256, 64) and tuple(P[nxt][0].shape) == (64, 256):
-                    # res2: the same pair as a streaming kernel (conv_b2b_narrow.hip)
-                    w1, b1 = P[nxt]
-                    key = p + "b2b"
-                    if key not in P:
-                        P[key] = pack_b2b_narrow(w3, w1)
-                    y3 = pool.get(n, y2.h, y2.w, 256)
-                    y1_next = pool.get(n, y2.h, y2.w, 64)
-                    fl = 2 * n * y2.h * y2.w * (64 * 256 + 256 * 64)
-                    nb_ = n * y2.h * y2.w * (64 + 256 + 256 + 64) * 2 + 2 * 256 * 64 * 2
-                    self.calls.append(FnCall(L.dafne_bottleneck_tail_head_narrow_hip,
-                                             (_lib.ptr(y2.t), _lib.ptr(sc.t), _lib.ptr(P[key]), _lib.ptr(b3), _lib.ptr(b1),
-                                              n, y2.h, y2.w, _lib.ptr(y3.t), _lib.ptr(y1_next.t)),
-                                             (y2, sc, P[key], b3, b1, y3, y1_next), "conv_b2b_narrow", flops=fl, nbytes=nb_))
-                    self.flops += fl
-                else:
-                    y3 = conv(p + "conv3", y2, 1, 1, 0, F_RELU | F_RES, res=sc)
-                pool.put(y2)
-                if b == 0 and sc is not None:
-                    pool.put(sc)
-                if not any(x is f for k, f in feats.items() if k in FPN_IN_FEATURES):
-                    pool.put(x)          # res3/res4 outputs stay alive for the FPN laterals
-                x = y3
-            feats["res%d" % (si + 2)] = x
-        self.stage_feats = feats
-        # FPN: laterals (+ top-down add fused) and 3x3 outputs
-        prev = None
-        outs = {}
-        for lvl in (5, 4, 3):
-            f = feats["res%d" % lvl]
-            lat = conv("fpn_lateral%d" % lvl, f, 1, 1, 0, F_UP if prev is not None else 0, res=prev)
-            outs["p%d" % lvl] = conv("fpn_output%d" % lvl, lat, 3, 1, 1, 0)
-            prev = lat
-        p6 = conv("p6", outs["p5"], 3, 2, 1, 0)
-        # P7 = conv(relu(P6)), P6 itself stays un-rectified as a head input: conv_wr rectifies its pixel operand on load
-        # (F_RELU_INPUT); p7_relu_in off, or a P7 that conv_wr does not take: a rectified copy of P6 (relu_copy)
-        w7, b7 = P["p7"]
-        ho7, wo7 = conv_out_hw(p6.h, p6.w, 3, 2, 1)
-        if (opt.p7_relu_in and wr_on and b7 is not None
-                and wr_takes(3, 2, p6.c, w7.shape[0], WR_NOMINAL_BATCH * ho7 * wo7)):
-            p7 = conv("p7", p6, 3, 2, 1, F_RELU_INPUT)
-        else:
-            p6r = pool.get(n, p6.h, p6.w, p6.c)
-            self.calls.append(FnCall(L.dafne_relu_copy_bf16_hip, (_lib.ptr(p6.t), _lib.ptr(p6r.t), p6.t.numel()),
-                                     (p6, p6r), "relu_copy"))
-            p7 = conv("p7", p6r, 3, 2, 1, 0)
-        outs["p6"], outs["p7"] = p6, p7
+                x, y1, x_compact = self._block(si, b, nb, len(STAGE_BLOCKS[depth]), x, y1, x_compact)
+            self.stage_feats["res%d" % (si + 2)] = x
+        outs = self._fpn()
+        self._top_block(outs)
         self.features = [outs[k] for k in ("p3", "p4", "p5", "p6", "p7")]
         self.head_start = len(self.calls)          # launches [0, head_start) are backbone + FPN, the rest the head
-        self.head = HeadPlan(weights, self.features, num_classes, device, pool, self, head_outputs) if with_head else None
+        self.head = HeadPlan(weights, self.features, num_classes, device, self.pool, self, head_outputs) if with_head else None
         # the split-K workspace is allocated and ZEROED here, on the stream the plan is built on, like every other buffer of the
         # plan.  (Round 4 zeroed it at the first launch: torch.zeros then ran on torch's current stream while the launch went
         # to the sub-batch's own stream -- with small images, where the GPU keeps up with the eager enqueue, the fill landed
@@ -1013,6 +753,221 @@ class DensePlan:
         # found in round 5 as test_batch_invariance_and_determinism / test_tta_packed_chunks... failing now and then.)
         if any(isinstance(c, WrCall) for c in self.calls):
             self.wr_ws.tensor()
+
+    def _launch(self, fn, name, operands, flops=0, nbytes=0):
+        self.calls.append(FnCall.of(fn, name, operands, flops, nbytes))
+        self.flops += flops
+
+    def _conv(self, key, tin, k, stride, pad, flags, res=None):
+        """One convolution layer of the packed weights P[key] on the kernel that takes it -> its output (from the pool)."""
+        L, P, opt, n = _lib.load(), self.P, self.opt, self.n
+        wgt, bias = P[key]
+        cin, cout = tin.c, wgt.shape[0]
+        ho, wo = conv_out_hw(tin.h, tin.w, k, stride, pad)
+        o = self.pool.get(n, ho, wo, cout)
+        # conv3x3_c64.hip: 65 -> 49 us per launch when it has the GPU to itself, but nothing in the timed 3-stream layout (its
+        # persistent workgroups hold every CU's LDS, so the other sub-batches' kernels cannot share the chip with it): opt-in
+        if (opt.conv_c64 and k == 3 and stride == 1 and pad == 1 and cin == 64 and cout == 64 and res is None
+                and (flags & ~F_RELU) == 0 and tuple(wgt.shape) == (64, 576) and bias is not None):
+            # res2 conv2: persistent kernel with the weights in registers (conv3x3_c64.hip)
+            self._launch(L.dafne_conv3x3_c64_hip, "conv3x3_c64", (tin, wgt, bias, n, ho, wo, 1 if flags & F_RELU else 0, o),
+                         flops=2 * n * ho * wo * 64 * 576, nbytes=2 * n * ho * wo * 64 * 2 + wgt.numel() * 2)
+            return o
+        q8 = P.get(key + ".fp8")
+        act_q8 = P.get("act_q8") or {}
+        fp8 = None
+        if q8 is not None and k == 3 and stride == 1 and res is None and not (flags & (F_F32 | F_UP | F_RES)):
+            if self.calib is not None:
+                self.calls.append(AmaxProbe(self.calib, key, [tin]))
+            elif key in act_q8:
+                fp8 = (q8[1] / act_q8[key], act_q8[key])       # oscale = weight scale / in_qscale
+        segs = [(tin.t, o.t, res.t if res is not None else None, tin.h, tin.w, ho, wo)]
+        c = ConvCall(q8[0] if fp8 else wgt, bias, cin, cout, k, stride, pad, flags, segs, n, fp8=fp8, shared_gpu=self.no_excl)
+        if (fp8 is None and opt.conv_wr and wr_takes(k, stride, cin, cout, WR_NOMINAL_BATCH * ho * wo) and bias is not None
+                and L.dafne_conv2d_wr_ok(ctypes.byref(c.prm), c.segs)):
+            # small-M layer (res5, FPN top): 128 px x 256 ch tiles, weights -> registers, split-K
+            c = WrCall(c, cached_pack(P, key + ".wr", lambda: pack_conv_frag(wgt)), self.wr_ws)
+        else:
+            assert not (flags & F_RELU_INPUT), "only conv_wr rectifies its input on load (the caller checks wr_takes)"
+            if fp8 is None and k == 3 and cin == 256 and opt.conv_rp and c.kernel_id() == 6 and c.rp_ok():
+                # 256-channel 3x3 layers the patch kernel would take (FPN outputs): resident-patch kernel
+                wfrag, f16 = rp_weights(P, key, wgt)
+                c = ConvCall(wgt, bias, cin, cout, k, stride, pad, flags,
+                             [(tin.t, o.t, None, tin.h, tin.w, ho, wo)], n, wfrag=wfrag, shared_gpu=self.no_excl, frag16=f16)
+        self.calls.append(c)
+        self.flops += c.flops
+        return o
+
+    def _stem(self):
+        """Preprocess output [N, H+6, W+6, 4] -> conv7x7/s2 -> maxpool -> (the pooled map, res2.0's conv1 output when the stem
+        kernel computed it or None)."""
+        L, P, opt, pool, n, h, w = _lib.load(), self.P, self.opt, self.pool, self.n, self.h, self.w
+        self.stem_in = torch.zeros(n, h + 6, w + 6, 4, dtype=BF16, device=self.device)
+        wgt, bias = P["stem"]
+        x = pool.get(n, h // 4, w // 4, 64)
+        stem_flops = 2 * n * (h // 2) * (w // 2) * 64 * 7 * 7 * 3
+        if not opt.fuse_stem:
+            stem_out = pool.get(n, h // 2, w // 2, 64)
+            c = ConvCall(wgt, bias, 4, 64, 7, 2, 3, F_RELU,
+                         [(self.stem_in, stem_out.t, None, h + 6, w + 6, h // 2, w // 2)], n, shared_gpu=self.no_excl)
+            self.calls.append(c)
+            self.flops += c.flops
+            self._launch(L.dafne_maxpool3x3s2_nhwc_bf16_hip, "maxpool", (stem_out, x, n, h // 2, w // 2, 64))
+            pool.put(stem_out)
+            return x, None
+        # conv7x7/s2 + ReLU + max-pool in one kernel: the half-resolution map never reaches HBM
+        c1 = P.get("res2.0.conv1")
+        if not (opt.fuse_stem_conv1 and c1 is not None and tuple(c1[0].shape) == (64, 64) and c1[1] is not None):
+            self._launch(L.dafne_stem_pool_hip, "stem_pool", (self.stem_in, wgt, bias, n, h, w, x), flops=stem_flops,
+                         nbytes=n * ((h + 6) * (w + 6) * 8 + (h // 4) * (w // 4) * 128))
+            return x, None
+        # ... and res2.0's first convolution (1x1, 64 -> 64, ReLU) on the pooled tile while it is in LDS
+        # (stem_pool.hip CONV1): the pooled map is not read back by a launch of its own (67 MB at batch 8)
+        y1 = pool.get(n, h // 4, w // 4, 64)
+        self._launch(L.dafne_stem_pool_conv1_hip, "stem_pool_conv1", (self.stem_in, wgt, bias, c1[0], c1[1], n, h, w, x, y1),
+                     flops=stem_flops + 2 * n * (h // 4) * (w // 4) * 64 * 64,
+                     nbytes=n * ((h + 6) * (w + 6) * 8 + (h // 4) * (w // 4) * 256))
+        return x, y1
+
+    def _fpn_input(self, a):
+        return any(a is f for k, f in self.stage_feats.items() if k in FPN_IN_FEATURES)
+
+    def _release(self, b, mid, sc, x, y3):
+        """What a block returns to the pool once its last launch is in the list -- ONE rule, in this order (the order of get and
+        put decides which buffer a later layer receives): the map between its layers that the last launch read (conv1's output,
+        or conv2's); block 0's projection output unless it became the block's output; the block's input unless it became the
+        output or is an FPN input feature (res3/res4 outputs stay alive for the FPN laterals)."""
+        self.pool.put(mid)
+        if b == 0 and sc is not None and sc is not y3:
+            self.pool.put(sc)
+        if x is not y3 and not self._fpn_input(x):
+            self.pool.put(x)
+
+    def _emit_block(self, e, p, b, nxt, x, sc, mid):
+        """Launch BLOCK_KERNELS entry `e` on block `p` ("resS.B."): x the block's input, sc its shortcut map (None: `e` fuses the
+        projection), mid conv1's output (conv2's when `e` does not fuse the 3x3), nxt the next block's conv1 key (None: the stage's
+        last block, the kernel's no-head form) -> (the block's output, the next block's conv1 output or None)."""
+        L, P, pool, n, c = _lib.load(), self.P, self.pool, self.n, e.c
+        proj = sc is None
+        (w2, b2), (w3, b3) = P[p + "conv2"], P[p + "conv3"]
+        w1, b1 = P[nxt] if nxt else (None, None)
+        wsc, bsc = P[p + "shortcut"] if proj else (None, None)
+        wgt, f16 = e.weights(P, p, w2, w3, w1, wsc)
+        scratch = None
+        if e.scratch:            # one buffer per kernel and plan, allocated on first use
+            scratch = cached_pack(self.scratch, e.scratch,
+                                  lambda: torch.empty(getattr(L, e.scratch)(), dtype=torch.uint8, device=self.device))
+        h, w = mid.h, mid.w
+        ho, wo = ((h + 1) // 2, (w + 1) // 2) if e.s2 else (h, w)
+        # whole-block kernels write Y = relu(conv3(T) + X) OVER X when X is dead after the block (an identity block's input, or
+        # block 0's projection output): a tile reads its own X rows and nobody else's (the halo is on the 3x3's input only), so
+        # the stores go to DRAM pages the same workgroup has just read (open rows, lines still in L2)
+        inplace = e.conv2 and not e.s2 and self._res_dead(sc, x, b)
+        y3 = sc if inplace else pool.get(n, ho, wo, 4 * c)
+        y1_next = pool.get(n, h, w, c) if nxt else None
+        px = n * ho * wo
+        flops = 2 * px * c * c * ((9 if e.conv2 else 0) + 4 + (4 if nxt else 0) + (4 if proj else 0))
+        # the weights as packed -- conv_bneck's no-head form counts its zero conv1 section, which it walks; conv_blk_narrow_s2
+        # counts conv2 and conv3 only (9 c^2 + 4 c^2), not the conv1 / projection sections of the pack it shares with conv_blk_narrow
+        wbytes = (13 * c * c if e.s2 else wgt.numel()) * 2
+        nbytes = (n * h * w * c + px * ((c if proj else 4 * c) + 4 * c + (c if nxt else 0))) * 2 + wbytes
+        name = e.name + ("_proj" if proj and e.proj == MAY else "") + ("" if nxt or e.head != MAY else "_last")
+        # the entry point's operands, in its order; an entry that CAN fuse a projection / a next conv1 has their operands, NULL
+        # for a block without one.  Second operand -- projection fused: the block input; otherwise the shortcut map
+        has_proj, has_head = e.proj != NEVER, e.head != NEVER
+        ops = [mid, x if proj else sc, wgt] + ([b2] if e.conv2 else []) + [b3] + ([bsc] if has_proj else []) + ([b1] if has_head else [])
+        ops += [n, h, w, y3] + ([y1_next] if has_head else []) + ([scratch, scratch.numel()] if e.scratch else [])
+        self._launch(getattr(L, e.entry16 if f16 else e.entry), name, ops, flops=flops, nbytes=nbytes)
+        self._release(b, mid, sc, x, y3)
+        return y3, y1_next
+
+    def _res_dead(self, sc, x, b):
+        # the shortcut operand is not needed after the block: block 0's projection output always; an identity block's input
+        # unless it is a retained feature
+        if not self.opt.inplace_res or sc is None:
+            return False
+        if b == 0:
+            return sc is not x
+        return not any(sc is f for f in self.stage_feats.values())
+
+    def _block(self, si, b, nb, n_stages, x, y1, x_compact):
+        """Bottleneck block b of stage res(si+2): shortcut / conv1, then the first BLOCK_KERNELS entry that takes the block,
+        otherwise the separate launches.  y1: conv1's output when the previous launch computed it (a fused tail, the stem);
+        x_compact: x holds only the even pixels.  -> (output, the next block's conv1 output or None, output is compact)."""
+        P, opt, calib = self.P, self.opt, self.calib
+        p = "res%d.%d." % (si + 2, b)
+        stride = 2 if (b == 0 and si > 0) else 1
+        nxt = "res%d.%d.conv1" % (si + 2, b + 1) if b + 1 < nb else None    # the stage's last block has no next conv1
+        w2, w3, w1 = P[p + "conv2"][0], P[p + "conv3"][0], P[nxt][0] if nxt else None
+        # res2.0: the projection shortcut is computed inside the fused tail (conv_b2b_narrow.hip, PROJ)
+        proj_fused = (opt.b2b_narrow_on and b == 0 and stride == 1 and nxt is not None and tuple(w3.shape) == (256, 64)
+                      and tuple(P[p + "shortcut"][0].shape) == (256, 64) and tuple(w1.shape) == (64, 256))
+        # (the whole-block kernel takes block 0 under the same conditions: its projection is fused as well)
+        in_stride = 1 if (b == 0 and x_compact) else stride      # (the previous stage's tail has applied the stride)
+        if b == 0:
+            sc = None if proj_fused else self._conv(p + "shortcut", x, 1, in_stride, 0, 0)
+        else:
+            sc = x
+        if y1 is None:                                           # (else: computed by the previous block's fused tail)
+            y1 = self._conv(p + "conv1", x, 1, in_stride, 0, F_RELU)    # STRIDE_IN_1X1
+        # what keeps an entry from a block whose shapes it takes
+        nx0 = "res%d.0." % (si + 3)
+        barred = {
+            # an fp8 model's conv2 takes e4m3 activations on the fp8 MFMA kernel (its definition): not fused;
+            # the stage's last block runs on the no-head form only with fuse_bneck_last
+            "conv_bneck": ((P.get(p + "conv2.fp8") is not None and (calib is not None or (p + "conv2") in (P.get("act_q8") or {})))
+                           or not (nxt or opt.fuse_bneck_last)),
+            # the last block of a stage nobody but the next stage reads is computed only at the pixels the next stage's stride-2
+            # 1x1 layers touch (conv_blk_narrow_s2.hip); off: the full map (A/B runs)
+            "conv_blk_narrow_s2": not (opt.res2_tail_s2 and calib is None and si + 1 < n_stages
+                                       and "res%d" % (si + 2) not in FPN_IN_FEATURES
+                                       # the only readers are the next stage's two 1x1 stride-2 layers (packed 1x1 weights: [Cout, Cin])
+                                       and tuple(P[nx0 + "conv1"][0].shape)[1:] == (256,)
+                                       and tuple(P[nx0 + "shortcut"][0].shape)[1:] == (256,)),
+            # block 0 only with its projection fused (the kernel has no form that reads a separate projection output)
+            "conv_blk_narrow": not (b > 0 or proj_fused),
+        }
+
+        def first(conv2, mid):
+            return next((e for e in BLOCK_KERNELS if e.conv2 == conv2 and not barred.get(e.name)
+                         and e.takes(opt, w2, w3, w1, proj_fused, mid.c)), None)
+
+        mid, e = y1, first(True, y1)
+        if e is None:
+            mid = self._conv(p + "conv2", y1, 3, 1, 1, F_RELU)
+            self.pool.put(y1)
+            e = first(False, mid)
+        if e is not None:
+            y3, y1_next = self._emit_block(e, p, b, nxt, x, sc, mid)
+            return y3, y1_next, e.s2
+        y3 = self._conv(p + "conv3", mid, 1, 1, 0, F_RELU | F_RES, res=sc)
+        self._release(b, mid, sc, x, y3)
+        return y3, None, False
+
+    def _fpn(self):
+        """FPN: laterals (+ top-down add fused) and 3x3 outputs -> {"p3", "p4", "p5"}."""
+        prev, outs = None, {}
+        for lvl in (5, 4, 3):
+            lat = self._conv("fpn_lateral%d" % lvl, self.stage_feats["res%d" % lvl], 1, 1, 0, F_UP if prev is not None else 0, res=prev)
+            outs["p%d" % lvl] = self._conv("fpn_output%d" % lvl, lat, 3, 1, 1, 0)
+            prev = lat
+        return outs
+
+    def _top_block(self, outs):
+        """P6 = conv(P5), P7 = conv(relu(P6)), both 3x3 stride 2, into outs."""
+        p6 = self._conv("p6", outs["p5"], 3, 2, 1, 0)
+        # P7 = conv(relu(P6)), P6 itself stays un-rectified as a head input: conv_wr rectifies its pixel operand on load
+        # (F_RELU_INPUT); p7_relu_in off, or a P7 that conv_wr does not take: a rectified copy of P6 (relu_copy)
+        w7, b7 = self.P["p7"]
+        ho7, wo7 = conv_out_hw(p6.h, p6.w, 3, 2, 1)
+        if (self.opt.p7_relu_in and self.opt.conv_wr and b7 is not None
+                and wr_takes(3, 2, p6.c, w7.shape[0], WR_NOMINAL_BATCH * ho7 * wo7)):
+            p7 = self._conv("p7", p6, 3, 2, 1, F_RELU_INPUT)
+        else:
+            p6r = self.pool.get(self.n, p6.h, p6.w, p6.c)
+            self._launch(_lib.load().dafne_relu_copy_bf16_hip, "relu_copy", (p6, p6r, p6.t.numel()))
+            p7 = self._conv("p7", p6r, 3, 2, 1, 0)
+        outs["p6"], outs["p7"] = p6, p7
 
     def run(self, stream=None):
         if self.graph is not None and stream is None:
