@@ -181,6 +181,12 @@ SIGNATURES = {
     "dafne_pred_dgrad_gn_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg)]),
     "dafne_pred_dgrad_gn_hip": (c_int, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg), c_void_p, ctypes.POINTER(c_void_p), c_int,
                                         ctypes.POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dafne_tower_wgrad_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg)]),
+    "dafne_tower_wgrad_hip": (c_int, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg), ctypes.POINTER(c_void_p), c_void_p, c_void_p,
+                                      c_size_t, c_void_p]),
+    "dafne_tower_dgrad_gn_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg)]),
+    "dafne_tower_dgrad_gn_hip": (c_int, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvSeg), c_void_p, ctypes.POINTER(c_void_p),
+                                         ctypes.POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dafne_bottleneck_body_scratch_bytes": (c_size_t, []),
     "dafne_bottleneck_body_hip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                           c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -31,6 +31,8 @@ PER_FILE = {
     # a matrix unit whose GroupNorm on load is written as scalar fp32: kept scalar (no packed fp32 at all in its listing)
     "conv_pred_wgrad.hip": ["-fno-slp-vectorize"],
     "conv_pred_dgrad.hip": ["-fno-slp-vectorize"],
+    "conv_tower_wgrad.hip": ["-fno-slp-vectorize"],
+    "conv_tower_dgrad.hip": ["-fno-slp-vectorize"],
 }
 
 

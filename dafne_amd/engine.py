@@ -712,8 +712,9 @@ class DensePlan:
     """Backbone + FPN + head for one (N, H, W): buffers + ordered launches."""
 
     def __init__(self, weights, n, h, w, depth, num_classes, device, with_head=True, head_outputs=None, calib=None,
-                 shared_gpu=False):
-        """calib (dict): build the CALIBRATION plan of an fp8 model -- every layer that could take its plain (not
+                 shared_gpu=False, keep_towers=False):
+        """keep_towers: the head keeps every tower layer's input maps out of the pool and records the tower launches (HeadPlan).
+        calib (dict): build the CALIBRATION plan of an fp8 model -- every layer that could take its plain (not
         GroupNorm-fed) input in e4m3 runs on the bf16 kernel and records max |input| under its weight key; the scales derived
         from it (act_qscale_from_amax) go into weights["act_q8"], and plans built afterwards route those layers to the fp8
         MFMA kernel (dafne_conv2d_nhwc_fp8w_hip with in_qscale = the layer's scale)."""
@@ -745,7 +746,8 @@ class DensePlan:
         self._top_block(outs)
         self.features = [outs[k] for k in ("p3", "p4", "p5", "p6", "p7")]
         self.head_start = len(self.calls)          # launches [0, head_start) are backbone + FPN, the rest the head
-        self.head = HeadPlan(weights, self.features, num_classes, device, self.pool, self, head_outputs) if with_head else None
+        self.head = HeadPlan(weights, self.features, num_classes, device, self.pool, self, head_outputs,
+                             keep_towers=keep_towers) if with_head else None
         # the split-K workspace is allocated and ZEROED here, on the stream the plan is built on, like every other buffer of the
         # plan.  (Round 4 zeroed it at the first launch: torch.zeros then ran on torch's current stream while the launch went
         # to the sub-batch's own stream -- with small images, where the GPU keeps up with the eager enqueue, the fill landed
@@ -1062,9 +1064,15 @@ class HeadPlan:
     [corners8|ctrness] (offset: base_corners folded into the bias), for iterative [c0..c3 tower parts|ctrness] followed by
     the corner chain (dafne_corner_chain_hip) into ``corners``.  Without centerness the prediction has 8 channels."""
 
-    def __init__(self, P, feats, num_classes, device, pool, plan, outputs=None):
+    def __init__(self, P, feats, num_classes, device, pool, plan, outputs=None, keep_towers=False):
         """outputs: optional {"logits"|"center"|"delta_ctr"|"corners": [5 fp32 NHWC tensors]} (the buffers the head mode
-        has, HeadOutputs.views) to write into (views of a larger batch's buffers when the batch is split over streams)."""
+        has, HeadOutputs.views) to write into (views of a larger batch's buffers when the batch is split over streams).
+        keep_towers (the plan slot of the tower backward, modeling/dafne/tower_backward.py): the intermediate tower maps are
+        NOT returned to the pool -- nothing else may write a layer's input between the forward and its weight gradient -- and
+        every tower layer is recorded like the prediction layers: tower_calls[(name, i)] = the layer's ConvCall (also when it
+        runs inside a ConvPairCall), tower_inputs[(name, i)] = (ins, gn_in).  The launch list and the arithmetic are the
+        same; only buffer identity differs."""
+        self.tower_calls, self.tower_inputs = {}, {}
         L = _lib.load()
         n = feats[0].n
         self.levels = feats
@@ -1162,6 +1170,9 @@ class HeadPlan:
                     c = ConvCall(wgt, bias, C, C, 3, 1, 1, flags, seg_list(cur, outs), n, gn_partial=partial, gn_in=cur_gn,
                                  gn_fin=fin, wfrag=wfrag, shared_gpu=sg, frag16=f16)
                 c.tower_tag = (name, i)
+                if keep_towers:
+                    self.tower_calls[(name, i)] = c
+                    self.tower_inputs[(name, i)] = (cur, cur_gn)
                 calls.append(c)
                 plan.flops += c.flops
                 gsegs = (_lib.GnSeg * len(outs))()
@@ -1183,7 +1194,7 @@ class HeadPlan:
                                          _lib.ptr(beta), ctypes.c_float(1e-5)), (outs, partial, stats, gamma, beta),
                                         "groupnorm"))
                     nxt_gn = None
-                if i > 0:
+                if i > 0 and not keep_towers:
                     for a in cur:
                         # cls_tower.i and <partner>.i may run in ONE launch: a map the cls tower has released must not be
                         # handed to the partner tower while the pair that still reads it is in flight (nor the other way)

@@ -7,8 +7,8 @@ respect to the finished head outputs (loss_function.py / dafne_losses_backward_h
     uncook_backward(...)                   dafne_head_uncook_backward_hip: finished regressions -> raw delta / center / scales
     backward_prediction_layers(model, b)   what OneStageDetector.backward_prediction_layers runs
 
-The last GroupNorm and bias of the complete towers are tail_backward.py's (DESIGN row F12); the rest of the towers, the FPN and the
-backbone have no backward: they stay frozen.
+The last GroupNorm and bias of the complete towers are tail_backward.py's (DESIGN row F12), their convolutions and other GroupNorms
+tower_backward.py's (DESIGN row F13); center_tower, the FPN and the backbone have no backward: they stay frozen.
 """
 import ctypes
 
@@ -138,14 +138,15 @@ def _accumulate(p, g):
         p.grad.add_(g)
 
 
-def backward_prediction_layers(model, batch, _tail=None):
+def backward_prediction_layers(model, batch, _tail=None, _slot="train"):
     """OneStageDetector.backward_prediction_layers: validation_losses' forward on a plan slot of its own, then target
     assignment (the forward's), the cooked loss forward + backward, the uncook kernel and three weight-gradient calls;
     accumulates into .grad of prediction_parameters(model) and returns validation_losses' dict (the same launches: the same
     bits).  Nothing is read back to the host.
     _tail (tail_backward.backward_head_tail): called as _tail(plan, None, None) once the plan is known and before any .grad is
     touched (it may refuse the plan), and as _tail(plan, g_logits, g_delta) after the last launch here, with the per-level loss
-    gradients with respect to the raw outputs of cls_logits and corners_pred (+ ctrness)."""
+    gradients with respect to the raw outputs of cls_logits and corners_pred (+ ctrness).
+    _slot: the plan slot the forward runs on ("towers", tower_backward.backward_towers: that plan keeps the tower maps)."""
     import torch.distributed as dist
     from ... import postprocess as pp
     from .loss_function import _backward_call
@@ -159,7 +160,7 @@ def backward_prediction_layers(model, batch, _tail=None):
                                   "a quantised model; fine-tune the bf16 one)")
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         raise NotImplementedError("backward_prediction_layers is single-process: no gradient all-reduce (DDP is out of scope)")
-    losses = model.validation_losses(batch, _slot="train")
+    losses = model.validation_losses(batch, _slot=_slot)
     last = model._last_validation
     plan, tg = last["plan"], last["targets"]
     hp = plan.head

@@ -7,7 +7,7 @@ convolution (dafne_pred_dgrad_gn_hip, csrc/conv_pred_dgrad.hip).
     backward_head_tail(model, batch)         what OneStageDetector.backward_head_tail runs
 
 The tensor it ends at, gx, is what a 256 -> 256 weight- or data-gradient kernel of tower convolution .9 takes as its output
-gradient; that convolution's weight and everything before it stay frozen.
+gradient: tower_backward.py (DESIGN row F13) goes on from there; here that convolution's weight and everything before it stay frozen.
 """
 import ctypes
 
@@ -88,12 +88,14 @@ def tail_parameters(model):
     return out
 
 
-def backward_head_tail(model, batch):
+def backward_head_tail(model, batch, _slot="train", _towers=None):
     """OneStageDetector.backward_head_tail: backward_prediction_layers (the same launches: the same bits for the losses and the
     prediction layers' gradients), then one pred_dgrad_gn call per complete tower on the loss gradients at the raw logits and at
     the raw corners (+ centerness) outputs; accumulates into .grad of tail_parameters(model) and returns the loss dict.  Keeps
     model._last_head_tail = {"plan", "gx": {tower: per-level list}, "g": {tower: the per-level gradients the call read}} (tests,
-    and the next slice of the tower backward)."""
+    and the next slice of the tower backward).
+    _slot / _towers (tower_backward.backward_towers): the plan slot, and a callback _towers(plan) that runs once the plan is known,
+    before any .grad is touched, and may refuse it."""
     import torch.distributed as dist
     head = model.proposal_generator.dafne_head
     if head.head_mode[0] == "iterative":
@@ -109,6 +111,8 @@ def backward_head_tail(model, batch):
     def tail(plan, g_logits, g_delta):
         calls = plan.head.pred_calls
         if g_logits is None:
+            if _towers is not None:
+                _towers(plan)
             for name, key in _TOWER_CALL:
                 if not (int(calls[key].prm.flags) & F_GNIN):
                     raise NotImplementedError("backward_head_tail needs prediction calls that normalise on load: with the engine switch "
@@ -127,6 +131,6 @@ def backward_head_tail(model, batch):
             _accumulate(tower[10].bias, dbeta)
         record.update(plan=plan, gx=gx, g=gout)
 
-    losses = backward_prediction_layers(model, batch, _tail=tail)
+    losses = backward_prediction_layers(model, batch, _tail=tail, _slot=_slot)
     model._last_head_tail = record
     return losses

@@ -124,6 +124,7 @@ class OneStageDetector(nn.Module):
         self.__dict__.pop("_counts_ring", None)
         self.__dict__.pop("_last_pred_backward", None)      # (holds a plan of the weights that were just replaced)
         self.__dict__.pop("_last_head_tail", None)
+        self.__dict__.pop("_last_towers", None)
         self._consts = {}
         if hasattr(self, "_pipe"):
             self._pipe = {}
@@ -277,7 +278,9 @@ class OneStageDetector(nn.Module):
     def plan(self, n, h, w, slot=0, graph=False):
         def build():
             nc = self.proposal_generator.dafne_head.num_classes
-            return engine.DensePlan(self._weights(), n, h, w, self.depth, nc, self.device)
+            # slot "towers" (backward_towers): the head keeps its intermediate tower maps; every other slot is what it was
+            kw = {"keep_towers": True} if slot == "towers" else {}
+            return engine.DensePlan(self._weights(), n, h, w, self.depth, nc, self.device, **kw)
         p = self._lru_get(self._plans, (n, h, w, slot), build)
         if graph:
             p.capture()
@@ -871,6 +874,26 @@ class OneStageDetector(nn.Module):
         off (the raw map is not kept there)."""
         from .dafne.tail_backward import backward_head_tail
         return backward_head_tail(self, batched_inputs)
+
+    # ------------------------------------------------------------ ... and the complete towers' convolutions and GroupNorms (DESIGN row F13)
+    def tower_parameters(self):
+        """tail_parameters() plus, for cls_tower and corners_tower, <tower>.9.weight and then for i = 2, 1, 0
+        <tower>.{3i+1}.weight, <tower>.{3i+1}.bias, <tower>.{3i}.bias, <tower>.{3i}.weight: what backward_towers differentiates
+        (45 tensors for the released head).  center_tower, the FPN and the backbone are not among them."""
+        from .dafne.tower_backward import tower_parameters
+        return tower_parameters(self)
+
+    def backward_towers(self, batched_inputs):
+        """backward_head_tail (same launches on a plan slot that keeps the tower maps: same bits for the losses and every
+        gradient of tail_parameters()), then per complete tower, from layer 3 down to layer 0, the weight gradient of the
+        layer's convolution (dafne_tower_wgrad_hip) and, above layer 0, its data gradient carried back through the ReLU and
+        the GroupNorm before it (dafne_tower_dgrad_gn_hip), which also gives that GroupNorm's affine gradient and the bias
+        gradient of the convolution before it.  ACCUMULATES into .grad of tower_parameters() and returns the loss dict.  No
+        data gradient leaves layer 0: center_tower, the FPN and the backbone stay frozen.  The per-layer gradients are kept in
+        _last_towers["g"][(tower, i)] until invalidate().  Raises NotImplementedError for the iterative head, the fp8 model,
+        more than one rank, and when a tower layer does not normalise on load (engine switches fuse_gn / fuse_gn_pred off)."""
+        from .dafne.tower_backward import backward_towers
+        return backward_towers(self, batched_inputs)
 
     def validation_losses_scenes(self, scenes, labels, patch_size=1024, overlap=200, batch=8, layout_hwc=None, filter_empty=True):
         """validation_losses on whole scenes and their scene-level labelTxt (evaluation.scene_eval.load_scene_labels, what

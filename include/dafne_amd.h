@@ -377,6 +377,51 @@ int dafne_pred_dgrad_gn_hip(const dafne_conv_params* prm, const dafne_conv_seg* 
                             const float* const* d_gout, int gout_ps, float* const* d_gx, float* d_dgamma, float* d_dbeta,
                             float* d_dbias, void* d_ws, size_t ws_bytes, void* stream);
 /*
+ * dafne_tower_wgrad_hip (ABI 156, conv_tower_wgrad.hip): the weight gradient of one 256 -> 256 tower convolution of the head
+ * (cls_tower / corners_tower .0 .3 .6 .9) -- 3x3 / stride 1 / pad 1 -- summed over every segment, image and pixel:
+ *     d_dw[co, ci, kh, kw] = sum g[s][n, y, x, co] * X[s][n, y + kh - 1, x + kw - 1, ci]
+ * prm / segs: the forward call's own description of its input, with Cin == Cout == 256 (flags GN_STATS, GN_INPUT, GN_FINALIZE,
+ * EXCLUSIVE and FRAG16 are accepted, anything else is DAFNE_E_INVALID; d_weight, d_bias, the output-side GroupNorm pointers and
+ * the segments' d_out are not read and may be NULL).  X: as for dafne_pred_wgrad_hip -- the stored haloed map, or with GN_INPUT
+ * GroupNorm + ReLU of it rounded to bf16, zero outside the image.  d_gout [n_segs] (a HOST array of device pointers): fp32 dense
+ * [N, Hout, Wout, 256] per segment.  d_dw: fp32 [256, 256, 3, 3] (OIHW); every element is written.  There is no bias gradient:
+ * it is d_dbias of the data-gradient call of the layer behind (dafne_tower_dgrad_gn_hip, dafne_pred_dgrad_gn_hip).
+ * Arithmetic: as dafne_pred_wgrad_hip (g as a hi + lo bf16 pair, fp32 accumulation per workgroup):
+ * |error| <= (2^-16 + n 2^-24) sum |g x| over the n summed pixels.  A workgroup owns a block of 64 output x 64 input channels
+ * of d_dw and a share of the tiles of 4 x 32 pixels: an input patch is staged (and normalised) once per 64 output channels.  No
+ * atomics: the launch is 16 blocks x P pixel splits, P = min(tiles, CUs / 16); split p writes slab p of d_ws, a second kernel adds
+ * the slabs in order in fp64 -- equal bits from run to run.  d_ws: dafne_tower_wgrad_workspace_bytes(prm, segs) = P * 256 * 2304 * 4
+ * bytes (0: refused parameters, or no device).
+ * Refusals, before any launch: NULL pointers, n_segs outside 1..5, GN_INPUT without statistics, unknown flags ->
+ * DAFNE_E_INVALID; not 256 -> 256, not 3x3 / stride 1 / pad 1, a segment above 2^20 pixels per image or 2^32 - 1 bytes of haloed
+ * input -> DAFNE_E_UNSUPPORTED; a small workspace -> DAFNE_E_WORKSPACE.
+ */
+size_t dafne_tower_wgrad_workspace_bytes(const dafne_conv_params* prm, const dafne_conv_seg* segs);
+int dafne_tower_wgrad_hip(const dafne_conv_params* prm, const dafne_conv_seg* segs, const float* const* d_gout, float* d_dw,
+                          void* d_ws, size_t ws_bytes, void* stream);
+/*
+ * dafne_tower_dgrad_gn_hip (ABI 156, conv_tower_dgrad.hip): the DATA gradient of one 256 -> 256 tower convolution of the head
+ * (.3 .6 .9), carried back through the ReLU and the GroupNorm the forward applies on load, to the raw output of the tower
+ * convolution before it.  The formulas and the meaning of every argument are dafne_pred_dgrad_gn_hip's with Cout = 256: prm /
+ * segs (GN_INPUT REQUIRED; flags as for dafne_tower_wgrad_hip), d_weight: the packed bf16 weight the forward multiplied,
+ * [256][256/64][3][3][64]; d_gout: fp32 dense [N, Hout, Wout, 256] per segment; d_gx: fp32 dense [N, Hout, Wout, 256] per
+ * segment; d_dgamma, d_dbeta, d_dbias: fp32 [256].  d_gout, d_gx and d_ws are aligned to 16 bytes.  Every element of all outputs
+ * is written.
+ * Arithmetic: v_mfma_f32_16x16x32_bf16 with exact bf16 weights and g as a hi + lo bf16 pair, fp32 accumulation over K = 2304.
+ * The weight is transposed into d_ws ([4 chunks of 64 co][9 taps][256 ci][64 co]) and streams through LDS; pass 1 stores gz =
+ * ga [a > 0] in d_gx, pass 2 is elementwise and in place.  No atomics: per-tile and per-workgroup partials in d_ws, added in a
+ * fixed order in fp64 -- equal bits from run to run.  d_ws: dafne_tower_dgrad_gn_workspace_bytes(prm, segs) bytes (0: refused
+ * parameters, or no device) = 1 179 648 + 4 * (512 * G1 + 64 * tiles + 64 * n_segs * n_images + 256 * G2), tiles of 4 x 32 pixels,
+ * G1 = min(tiles, CUs), G2 = min(ceil(pixels / 4), 8 * CUs).
+ * Refusals, before any launch: NULL or misaligned pointers, n_segs outside 1..5, GN_INPUT missing or without statistics, unknown
+ * flags -> DAFNE_E_INVALID; not 256 -> 256, not 3x3 / stride 1 / pad 1, the forward call's 32-bit offset limits ->
+ * DAFNE_E_UNSUPPORTED; a small workspace -> DAFNE_E_WORKSPACE.
+ */
+size_t dafne_tower_dgrad_gn_workspace_bytes(const dafne_conv_params* prm, const dafne_conv_seg* segs);
+int dafne_tower_dgrad_gn_hip(const dafne_conv_params* prm, const dafne_conv_seg* segs, const void* d_weight,
+                             const float* const* d_gout, float* const* d_gx, float* d_dgamma, float* d_dbeta, float* d_dbias,
+                             void* d_ws, size_t ws_bytes, void* stream);
+/*
  * fp8-weight twin (BASELINE config 5: "fp8 weights, CDNA4 fp8 MFMA conv path"; SURVEY 8(b) item 5
  * dafne_conv2d_nhwc_{bf16,fp8w}_hip).  The reference has no fp8 path: this entry DEFINES it.
  *   d_weight   OCP e4m3 bytes [Cout][Cin/64][KH][KW][64] (same K order as the bf16 layout, 1 byte per element)

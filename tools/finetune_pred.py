@@ -12,6 +12,8 @@ with checkpoint.save_checkpoint (tools/eval_net.py --weights loads it).
 
 --tail: also each complete tower's last GroupNorm affine and last convolution bias (cls_tower / corners_tower .10.weight, .10.bias,
 .9.bias; DESIGN row F12): OneStageDetector.tail_parameters through backward_head_tail.
+--towers (implies --tail): the whole of cls_tower and corners_tower, four convolutions and four GroupNorms each (DESIGN row F13):
+OneStageDetector.tower_parameters through backward_towers.  center_tower, the FPN and the backbone stay frozen.
 """
 import argparse
 import json
@@ -38,6 +40,8 @@ def main(argv=None):
     ap.add_argument("--overlap", type=int, default=200)
     ap.add_argument("--tail", action="store_true", help="also train the last GroupNorm affine and last convolution bias of "
                                                         "cls_tower and corners_tower (backward_head_tail)")
+    ap.add_argument("--towers", action="store_true", help="also train every convolution and GroupNorm of cls_tower and corners_tower "
+                                                          "(backward_towers; implies --tail)")
     ap.add_argument("--out", required=True, help="checkpoint to write")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides")
     args = ap.parse_args(argv)
@@ -73,8 +77,13 @@ def main(argv=None):
     classnames = (list(de.CLASSNAMES_DOTA_1_0) + ["container-crane"])[:cfg.MODEL.DAFNE.NUM_CLASSES]
     labels = load_scene_labels(args.scene_labels, names, classnames)
     # SOLVER.MOMENTUM; a config that does not set it gets detectron2's default (0.9)
-    opt = torch.optim.SGD(model.tail_parameters() if args.tail else model.prediction_parameters(), lr=args.lr, momentum=float(cfg.SOLVER.get("MOMENTUM", 0.9)),
-                          weight_decay=args.weight_decay)
+    if args.towers:
+        params, backward = model.tower_parameters(), model.backward_towers
+    elif args.tail:
+        params, backward = model.tail_parameters(), model.backward_head_tail
+    else:
+        params, backward = model.prediction_parameters(), model.backward_prediction_layers
+    opt = torch.optim.SGD(params, lr=args.lr, momentum=float(cfg.SOLVER.get("MOMENTUM", 0.9)), weight_decay=args.weight_decay)
     stream = scene_train_batches(cfg, scenes, labels, batch=args.batch, seed=args.seed, patch_size=args.patch_size,
                                  overlap=args.overlap, device=dev)
     with torch.cuda.device(dev):
@@ -82,7 +91,7 @@ def main(argv=None):
             if step >= args.steps:
                 break
             opt.zero_grad(set_to_none=True)
-            losses = model.backward_head_tail(tb) if args.tail else model.backward_prediction_layers(tb)
+            losses = backward(tb)
             opt.step()
             model.invalidate()
             print(json.dumps(dict({"step": step, "tiles": len(tb)}, **{k: float(v) for k, v in sorted(losses.items())})))
