@@ -9,6 +9,7 @@ forward() is one fused device pipeline -- uint8 image -> normalise/pad kernel ->
 ResNet-FPN -> head -> decode/top-k -> rotated NMS -> rescale/clip/gather -- with a
 single host sync at the very end (detection counts).
 """
+import collections
 import ctypes
 import os
 
@@ -25,8 +26,31 @@ from .dafne.dafne import head_levels
 
 _STREAMS = {}
 
+# a detect_packed(defer=True) step whose post-process is still to be enqueued: _post_process' arguments, `wait_events` being the
+# events at the end of the step's sub-batch streams
+_Deferred = collections.namedtuple("_Deferred", "st slot wait_events sizes do_postprocess strides main")
+
 
 SUBBATCH_WEIGHTS = {2: (5, 3), 3: (3, 2, 3)}
+# A batch too small to split (the reference's own loop: ONE image per call, tools/plain_train_net.py:316-336) rotates over the
+# compute streams, call by call: the convolutions of image i + 1 run beside those of image i on another plan set -- at batch 1 a
+# res4 block is 32 tiles for 256 CUs.
+B1_ROTATE = True
+B1_STREAMS = 3
+# ... and has FOUR plan sets (a split batch: two): a set is reusable only when its post-process has finished, which starts at the
+# NEXT call's head towers.
+B1_PLAN_SETS = 4
+
+
+def _pad32(v):
+    return (v + 31) // 32 * 32
+
+
+def hip_graphs_on(graphs, cfg_on, env):
+    """Replay a plan's launches from a HIP graph?  graphs: detect_packed's argument (None: the config decides, False: never);
+    cfg_on: cfg.ENGINE.HIP_GRAPHS; env: the value of DAFNE_HIP_GRAPHS or None ("1" / "0" overrides the config: A/B runs).  Read at
+    every call of either path."""
+    return graphs is not False and env != "0" and (bool(graphs) or bool(cfg_on) or env == "1")
 
 
 def subbatch_bounds(n, splits):
@@ -92,16 +116,11 @@ class OneStageDetector(nn.Module):
         if cfg.MODEL.TOP_MODULE.NAME:
             raise NotImplementedError("MODEL.TOP_MODULE is not used by any released config")
         self.depth = cfg.MODEL.RESNETS.DEPTH
-        self._packed = None
-        self._plans = {}
-        self._graphs = {}
-        self.__dict__.pop("_plan_lru", None)      # (its entries reference the caches they describe)
-        self._act_q8 = None         # fp8 model: calibrated activation scales {weight key: in_qscale} (calibrate_fp8)
-        self.side_stream = None
-        self._consts = {}
-        self._last_head = None
-        self.use_graphs = False     # optional: replay each sub-batch's dense plan from a HIP graph (no gain
-                                    # measured at batch 8: the GPU, not the host, is the bottleneck)
+        # every piece of runtime state is declared here or in invalidate(), which runs last: nothing is created on first use
+        self.side_stream = None     # the post-process stream of the pipelined path (shared by the process, _shared_stream)
+        self._last_head = None      # (tests: the head outputs the returned detections were decoded from)
+        self._last_validation = None        # (tests: what validation_losses computed its values from)
+        self.invalidate()
         self.eval()
 
     @property
@@ -109,25 +128,27 @@ class OneStageDetector(nn.Module):
         return self.pixel_mean.device
 
     # ------------------------------------------------------------ engine state
+    def _drop_plans(self):
+        """The launch plans are stale (other activation scales, other weights): drop their caches."""
+        self._plans = {}            # (n, h, w, slot) -> DensePlan of the one-stream path (plan())
+        self._pipe = {}             # (n, h, w, splits[, "even"]) -> the sub-batch pipeline of that shape (_pipe_state)
+        self._plan_lru = collections.OrderedDict()      # (id(cache), key) -> [cache, bytes] over both, oldest first (_lru_get)
+
     def invalidate(self):
         """Call after changing parameters: weights are re-packed lazily."""
+        self._drop_plans()
         self._packed = None
-        self._plans = {}
-        self._graphs = {}
-        self.__dict__.pop("_plan_lru", None)      # (its entries reference the caches they describe)
-        self._act_q8 = None
-        self._pending = None
-        self.__dict__.pop("_deferred", None)
-        self.__dict__.pop("_deferred_res", None)
-        self.__dict__.pop("_stream_q", None)
-        self.__dict__.pop("_staging", None)          # pinned / device staging of forward_streamed's host tiles
-        self.__dict__.pop("_counts_ring", None)
-        self.__dict__.pop("_last_pred_backward", None)      # (holds a plan of the weights that were just replaced)
-        self.__dict__.pop("_last_head_tail", None)
-        self.__dict__.pop("_last_towers", None)
-        self._consts = {}
-        if hasattr(self, "_pipe"):
-            self._pipe = {}
+        self._act_q8 = None         # fp8 model: calibrated activation scales {weight key: in_qscale} (calibrate_fp8)
+        self._consts = {}           # small constant device tensors (_dev_const)
+        self._deferred = None       # the detect_packed(defer=True) step whose post-process is still to be enqueued (_Deferred)
+        self._deferred_res = None   # ... its results, when an immediate call had to complete it (flush_deferred hands them out)
+        self._stream_q = []         # forward_streamed's batches in flight, oldest first: [out_hw, packed results or None]
+        self._stream_rot = 0        # ... and the compute stream its next unsplit batch starts on
+        self._staging = None        # pinned / device staging of forward_streamed's host tiles (_pack_inputs)
+        self._counts_ring = None    # pinned host buffers of the detection counts and rows (_stage_counts)
+        self._last_pred_backward = None     # (tests; holds a plan of the weights that were just replaced)
+        self._last_head_tail = None
+        self._last_towers = None
         self.backbone.invalidate()
         self.proposal_generator.dafne_head.invalidate()
 
@@ -159,11 +180,7 @@ class OneStageDetector(nn.Module):
         engine.check_act_qscales(scales)
         self._act_q8 = scales
         self._packed["act_q8"] = dict(self._act_q8)
-        self._plans = {}
-        self._graphs = {}
-        self.__dict__.pop("_plan_lru", None)      # (its entries reference the caches they describe)
-        if hasattr(self, "_pipe"):
-            self._pipe = {}
+        self._drop_plans()
 
     def check_fp8_act_scale_keys(self, scales):
         """Does `scales` ({weight key: in_qscale}) name exactly the layers this model quantises on load?  Raises ValueError
@@ -194,37 +211,45 @@ class OneStageDetector(nn.Module):
         every rank must call this (it is a collective)."""
         if self.cfg.ENGINE.WEIGHT_DTYPE != "fp8_e4m3":
             raise RuntimeError("calibrate_fp8: ENGINE.WEIGHT_DTYPE is %r" % (self.cfg.ENGINE.WEIGHT_DTYPE,))
-        L = _lib.load()
-        if layout_hwc:
-            n, h, w, _ = images_u8.shape
-        else:
-            n, _, h, w = images_u8.shape
-        hn, wn = (h + 31) // 32 * 32, (w + 31) // 32 * 32
+        n, h, w = self._image_dims(images_u8, layout_hwc)
         P = dict(self._weights())
         P.pop("act_q8", None)
         calib = {}
         nc = self.proposal_generator.dafne_head.num_classes
         with torch.cuda.device(images_u8.device):
-            plan = engine.DensePlan(P, n, hn, wn, self.depth, nc, self.device, calib=calib)
-            mean = (ctypes.c_float * 3)(*[float(v) for v in self.cfg.MODEL.PIXEL_MEAN])
-            std = (ctypes.c_float * 3)(*[float(v) for v in self.cfg.MODEL.PIXEL_STD])
-            vt = None
-            if valid_hw is not None and any(tuple(v) != (h, w) for v in valid_hw):
-                vt = torch.tensor([tuple(v) for v in valid_hw], dtype=torch.int32).to(self.device)
-            _lib.check(L.dafne_preprocess_image_hip(_lib.ptr(images_u8.contiguous()), int(layout_hwc), n, h, w, _lib.ptr(vt),
-                                                    mean, std, hn, wn, _lib.ptr(plan.stem_in), _lib.current_stream()),
-                       "dafne_preprocess_image_hip")
+            plan = engine.DensePlan(P, n, _pad32(h), _pad32(w), self.depth, nc, self.device, calib=calib)
+            self._preprocess_into(plan, images_u8.contiguous(), valid_hw, layout_hwc)
             plan.run()
             torch.cuda.synchronize()
         calib = engine.reduce_amax_over_ranks(calib, group, device=self.device)
         self._act_q8 = {k: engine.act_qscale_from_amax(v) for k, v in calib.items()}
         self._packed["act_q8"] = dict(self._act_q8)
-        self._plans = {}
-        self._graphs = {}
-        self.__dict__.pop("_plan_lru", None)      # (its entries reference the caches they describe)
-        if hasattr(self, "_pipe"):
-            self._pipe = {}
+        self._drop_plans()
         return dict(self._act_q8)
+
+    @staticmethod
+    def _image_dims(images_u8, layout_hwc):
+        """(n, h, w) of a uint8 batch [N,3,H,W], or [N,H,W,3] with layout_hwc."""
+        if layout_hwc:
+            n, h, w, _ = images_u8.shape
+        else:
+            n, _, h, w = images_u8.shape
+        return n, h, w
+
+    def _preprocess_into(self, plan, imgs, valid_hw, layout_hwc=False):
+        """The engine's load kernel on the current stream: contiguous uint8 images (valid_hw: their true sizes, None: all full
+        size) -> normalised, zero-padded to a multiple of 32, into plan.stem_in.  Returns the device tensor of the sizes it read
+        (None when every image is full size; _dev_const keeps it)."""
+        n, h, w = self._image_dims(imgs, layout_hwc)
+        mean = (ctypes.c_float * 3)(*[float(v) for v in self.cfg.MODEL.PIXEL_MEAN])
+        std = (ctypes.c_float * 3)(*[float(v) for v in self.cfg.MODEL.PIXEL_STD])
+        vt = None
+        if valid_hw is not None and any(tuple(v) != (h, w) for v in valid_hw):
+            vt = self._dev_const(valid_hw, torch.int32, (n, 2))
+        _lib.check(_lib.load().dafne_preprocess_image_hip(_lib.ptr(imgs), int(layout_hwc), n, h, w, _lib.ptr(vt), mean, std,
+                                                          _pad32(h), _pad32(w), _lib.ptr(plan.stem_in), _lib.current_stream()),
+                   "dafne_preprocess_image_hip")
+        return vt
 
     def _dev_const(self, values, dtype, shape):
         """Small constant device tensors (per-image sizes) are uploaded once and reused: a
@@ -245,8 +270,7 @@ class OneStageDetector(nn.Module):
         around the build -- on datasets where nearly every batch has its own (H, W) the entry count alone let the caches grow to
         whatever 48 + 48 shapes happen to weigh.  Before an entry is dropped the device is synchronised: its launches may still be
         queued, and its buffers go back to the allocator."""
-        import collections
-        lru = self.__dict__.setdefault("_plan_lru", collections.OrderedDict())      # (id(cache), key) -> [cache, bytes], oldest first
+        lru = self._plan_lru
         tag = (id(cache), key)
         if key in cache:
             cache[key] = cache.pop(key)              # dicts keep insertion order: most recently used last
@@ -288,7 +312,7 @@ class OneStageDetector(nn.Module):
 
     # ------------------------------------------------------------ fused path
     def detect_packed(self, images_u8, valid_hw=None, out_hw=None, layout_hwc=False, do_postprocess=True,
-                      pipelined=False, splits=1, stream_offset=0, graphs=None, defer=False, even=False, post_per_split=False):
+                      pipelined=False, splits=1, stream_offset=0, graphs=None, defer=False, even=False):
         """images_u8: device uint8 [N,3,H,W] (or [N,H,W,3] with layout_hwc) BGR.
         valid_hw: optional per-image (h, w) true sizes; out_hw: optional per-image
         requested output (height, width).  Returns (rows [N,k_cap,18], counts [N])
@@ -302,7 +326,7 @@ class OneStageDetector(nn.Module):
         The returned tensors are then produced on `self.side_stream`: wait on it (or
         torch.cuda.synchronize()) before reading them.  stream_offset rotates the compute streams the
         sub-batches use: consecutive calls with different offsets (the TTA wrapper's chunks) run concurrently.
-        graphs: replay the sub-batches' dense launches from HIP graphs (None: cfg.ENGINE.HIP_GRAPHS).  Worth it for a loop over
+        graphs: replay the dense launches from HIP graphs (None: cfg.ENGINE.HIP_GRAPHS; hip_graphs_on).  Worth it for a loop over
         one shape (host enqueue 1.9 -> 0.4 ms per step); the TTA wrapper's 27 views of 9 shapes pass False (GPU-bound at 26.7
         ms per image either way, and every shape's capture costs ~10 ms).
         defer=True (pipelined only; a LOOP's form): this call enqueues its convolutions and then the decode / NMS / rescale of
@@ -311,11 +335,7 @@ class OneStageDetector(nn.Module):
         the backbone's chip-wide launches they cost 3.7 % of the step (scratch/no_post.py, defer_post.py: +1.4 .. +4 %).
         Returns the PREVIOUS call's (rows, counts) -- None on the first call; flush_deferred() enqueues and returns the last.
         even=True: sub-batches of EQUAL size (a lone step with a host wait behind it ends when its longest stream does; the unequal
-        sizes of subbatch_bounds pay only in a loop whose steps overlap -- or with post_per_split).
-        post_per_split=True (immediate form only; forward()'s, round 6): decode / rotated NMS / rescale run per SUB-BATCH on the side
-        stream, smallest sub-batch first, each as soon as its own convolutions are done -- with unequal sub-batches the post-process
-        of the short one runs under the long one's convolutions and only the long one's own share trails the step.  Per-image
-        results are those of the whole-batch post-process (every image is decoded and suppressed on its own)."""
+        sizes of subbatch_bounds pay only in a loop whose steps overlap)."""
         if not images_u8.is_cuda or images_u8.dtype != torch.uint8:
             raise RuntimeError("detect_packed needs a uint8 CUDA tensor (the MI355X engine has no CPU path)")
         if self.cfg.ENGINE.WEIGHT_DTYPE == "fp8_e4m3" and self._act_q8 is None:
@@ -332,109 +352,32 @@ class OneStageDetector(nn.Module):
                 raise RuntimeError("fp8 model without activation scales: call calibrate_fp8(batch) or set_fp8_act_scales(scales) "
                                    "first (ENGINE.FP8_ACT_CALIBRATION=%r; 'off' runs only the GroupNorm-fed tower layers in "
                                    "e4m3, 'first_batch' calibrates on whatever batch comes first)" % (mode,))
-        L = _lib.load()
-        if layout_hwc:
-            n, h, w, _ = images_u8.shape
-        else:
-            n, _, h, w = images_u8.shape
-        hn, wn = (h + 31) // 32 * 32, (w + 31) // 32 * 32
-        mean = (ctypes.c_float * 3)(*[float(v) for v in self.cfg.MODEL.PIXEL_MEAN])
-        std = (ctypes.c_float * 3)(*[float(v) for v in self.cfg.MODEL.PIXEL_STD])
-        all_full = valid_hw is None or all(tuple(v) == (h, w) for v in valid_hw)
+        if defer and not pipelined:
+            raise ValueError("detect_packed(defer=True) is a form of the pipelined step")
+        n, h, w = self._image_dims(images_u8, layout_hwc)
         if valid_hw is None:
             valid_hw = [(h, w)] * n
         if out_hw is None:
             out_hw = valid_hw
         sizes = self._dev_const([(vh, vw, oh, ow, vh, vw) for (vh, vw), (oh, ow) in zip(valid_hw, out_hw)],
                                 torch.float32, (n, 6))
-        outs = self.proposal_generator.dafne_outputs
         strides = self.proposal_generator.fpn_strides
-
-        def dense(imgs, lo, hi, plan):
-            vt = None if all_full else self._dev_const(valid_hw[lo:hi], torch.int32, (hi - lo, 2))
-            _lib.check(L.dafne_preprocess_image_hip(_lib.ptr(imgs), int(layout_hwc), hi - lo, h, w, _lib.ptr(vt),
-                                                    mean, std, hn, wn, _lib.ptr(plan.stem_in),
-                                                    _lib.current_stream()), "dafne_preprocess_image_hip")
-            plan.run()
-
-        if defer and not pipelined:
-            raise ValueError("detect_packed(defer=True) is a form of the pipelined step")
+        replay = hip_graphs_on(graphs, self.cfg.ENGINE.HIP_GRAPHS, os.environ.get("DAFNE_HIP_GRAPHS"))
         with torch.cuda.device(images_u8.device):
             images_u8 = images_u8.contiguous()
-            if not defer and self.__dict__.get("_deferred") is not None:
+            if not defer and self._deferred is not None:
                 # a deferred post-process is pending and this call is not part of that loop: run it first (its plan set's
                 # head outputs must be read before anything reuses them); flush_deferred() hands the result out
-                self.__dict__["_deferred_res"] = self._run_deferred(self.__dict__.pop("_deferred"), ())
+                pending, self._deferred = self._deferred, None
+                self._deferred_res = self._run_deferred(pending, ())
             if not pipelined:
-                plan = self.plan(n, hn, wn)
-                genv = os.environ.get("DAFNE_HIP_GRAPHS")
-                if (self.cfg.ENGINE.HIP_GRAPHS if graphs is None else bool(graphs)) and genv != "0" and plan.graph is None:
-                    # a shape's SECOND call captures its launch list (the first ran eagerly: streams bind to hardware queues
-                    # at their first submission, see the pipelined branch): model([one image]) in a loop -- the reference's
-                    # own evaluation / benchmark loop, tools/benchmark.py:117-145 -- is host-bound when ~200 launches are
-                    # enqueued one by one (bench.py latency_b1)
-                    plan._uses = getattr(plan, "_uses", 0) + 1
-                    if plan._uses >= 2:
-                        plan.capture()
-                dense(images_u8, 0, n, plan)
-                self._last_head = plan.head          # (tests: the head outputs the returned detections were decoded from)
-                if getattr(self.cfg.ENGINE, "CHECK_FINITE", False):
-                    # the FPN maps first: behind them GroupNorm-on-load computes max(a x + b, 0), which turns a NaN into 0 again
-                    hd = plan.head
-                    for l, ft in enumerate(plan.features):
-                        # the buffers of the head's mode: no center without center_pred, chain output of the iterative head
-                        for nme, t in (("FPN map", ft.t), ("logits", hd.logits[l]), ("delta / ctrness", hd.delta_ctr[l]),
-                                       ("center", hd.center[l] if hd.center is not None else None),
-                                       ("corners", hd.corners[l] if hd.corners is not None else None)):
-                            if t is not None and not bool(torch.isfinite(t).all()):
-                                raise _lib.DafneHipError("ENGINE.CHECK_FINITE: non-finite %s at level %d (weights / input overflow? a NaN "
-                                                         "accumulator of a non-ReLU layer turns into -inf)" % (nme, l))
-                return outs.predict_packed(head_levels(plan.head, strides), sizes=sizes,
-                                           scale_corners=do_postprocess)
+                return self._detect_one_stream(images_u8, valid_hw, layout_hwc, sizes, do_postprocess, replay)
             # ---- pipeline: [preprocess, convs (split over `splits` streams), decode] | [NMS, gather]
             splits = max(1, min(int(splits), n))
             main = torch.cuda.current_stream()
             if self.side_stream is None:
                 self.side_stream = _shared_stream(images_u8.device, "side", 0)
-                self._pipe = {}
-            key = (n, hn, wn, splits, "even") if (even and splits > 1) else (n, hn, wn, splits)
-            if post_per_split and not defer and splits > 1:
-                key = key + ("pps",)
-
-            def build_pipe():
-                nc = self.proposal_generator.dafne_head.num_classes
-                bounds = [(k * n) // splits for k in range(splits + 1)] if even else subbatch_bounds(n, splits)
-                # two complete plan sets (A/B) with their own head-output buffers: decode + NMS of
-                # call i run on the side stream while call i+1's convolutions already write set B
-                hos, plan_sets = [], []
-                # plan sets (each with its own head-output buffers): two for a batch that is split over the compute streams; FOUR
-                # for a batch too small to split (one image per call), whose consecutive calls run on alternating streams -- a
-                # set is reusable only when its post-process has finished, which starts at the NEXT call's head towers
-                nsets = 2 if splits > 1 else max(2, int(os.environ.get("DAFNE_B1_SETS", "4")))
-                for _ in range(nsets):
-                    ho = engine.HeadOutputs(n, hn, wn, nc, self._weights()["scales"], self.device,
-                                            head_mode=self._weights()["head_mode"])
-                    hos.append(ho)
-                    plan_sets.append([engine.DensePlan(self._weights(), bounds[k + 1] - bounds[k], hn, wn, self.depth,
-                                                       nc, self.device, head_outputs=ho.views(bounds[k], bounds[k + 1]),
-                                                       shared_gpu=True)
-                                      for k in range(splits)])
-                # compute streams are high-priority: ROCm maps normal-priority streams onto a small shared set
-                # of hardware queues, and two sub-batches landing on one queue serialise (dense part alone,
-                # 4 splits: 714 -> 960 img/s); the high-priority pool gives each its own queue.  With the
-                # post-process stream in the mix 3 splits measured best (scratch/split_sweep.sh)
-                return {"i": 0, "cs": [_shared_stream(images_u8.device, "compute", k) for k in range(splits)], "ho": hos,
-                        "plans": plan_sets, "bounds": bounds, "cand": [None] * nsets, "done": [None] * nsets, "runs": [0] * nsets,
-                        "cand_split": [[None] * splits for _ in range(nsets)]}
-            if key not in self._pipe:
-                self._lru_get(self._pipe, key, build_pipe)
-                # plan building enqueued buffer fills, weight packing and uploads on the caller's stream: finished before any
-                # sub-batch stream touches the plans (once per shape; the steps themselves never wait for the host).  The
-                # streams are ordered behind it by `inputs_ready` as well; this makes a new shape's first step independent of it
-                torch.cuda.synchronize(images_u8.device)
-            else:
-                self._lru_get(self._pipe, key, build_pipe)
-            st = self._pipe[key]
+            st = self._pipe_state(n, _pad32(h), _pad32(w), splits, even, images_u8.device)
             slot = st["i"] % len(st["plans"])
             st["i"] += 1
             cs, plans, bounds = st["cs"], st["plans"][slot], st["bounds"]
@@ -443,14 +386,7 @@ class OneStageDetector(nn.Module):
                 cs = [_shared_stream(images_u8.device, "compute", (int(stream_offset) + k) % 3) for k in range(splits)]
             inputs_ready = torch.cuda.Event()
             inputs_ready.record(main)
-            vts = []
-            dbg = getattr(self, "_dbg_events", None)        # scratch/pipe_events.py: timestamps of the step's phases
-
-            def mark(tag, k, stream):
-                if dbg is not None:
-                    e = torch.cuda.Event(enable_timing=True)
-                    e.record(stream)
-                    dbg.append((st["i"], tag, k, e))
+            vts = []                                      # the sub-batches' size tensors, held until the step is enqueued
             for k in range(splits):
                 lo, hi = bounds[k], bounds[k + 1]
                 cs[k].wait_event(inputs_ready)
@@ -460,102 +396,138 @@ class OneStageDetector(nn.Module):
                 # dropped it (the read queues behind the previous call's network): tell the caching allocator
                 images_u8.record_stream(cs[k])
                 with torch.cuda.stream(cs[k]):
-                    vt = None if all_full else self._dev_const(valid_hw[lo:hi], torch.int32, (hi - lo, 2))
-                    vts.append(vt)
-                    sub = images_u8[lo:hi]
-                    _lib.check(L.dafne_preprocess_image_hip(_lib.ptr(sub), int(layout_hwc), hi - lo, h, w, _lib.ptr(vt),
-                                                            mean, std, hn, wn, _lib.ptr(plans[k].stem_in),
-                                                            _lib.current_stream()), "dafne_preprocess_image_hip")
-                mark("pre", k, cs[k])
+                    vts.append(self._preprocess_into(plans[k], images_u8[lo:hi], valid_hw[lo:hi], layout_hwc))
+            tower_evs = self._enqueue_dense(st, slot, cs, defer, replay)
+            ends = []
+            for k in range(splits):
+                ev = torch.cuda.Event()
+                ev.record(cs[k])
+                ends.append(ev)
+            if not defer:
+                return self._post_process(st, slot, ends, sizes, do_postprocess, strides, main)
+            prev = self._deferred
+            # (object.__setattr__: nn.Module's own costs 1.7 us, which the one-image streamed loop shows: +3 us per image)
+            object.__setattr__(self, "_deferred", _Deferred(st, slot, ends, sizes, do_postprocess, strides, main))
+            return self._run_deferred(prev, tower_evs) if prev is not None else None
+
+    def _detect_one_stream(self, images_u8, valid_hw, layout_hwc, sizes, do_postprocess, graphs):
+        """The whole batch on the caller's stream: preprocess, one plan, decode / NMS / rescale.  graphs: hip_graphs_on's answer."""
+        n, h, w = self._image_dims(images_u8, layout_hwc)
+        plan = self.plan(n, _pad32(h), _pad32(w))
+        if graphs and plan.graph is None:
+            # a shape's SECOND call captures its launch list (the first ran eagerly: streams bind to hardware queues
+            # at their first submission, see _enqueue_dense): model([one image]) in a loop -- the reference's
+            # own evaluation / benchmark loop, tools/benchmark.py:117-145 -- is host-bound when ~200 launches are
+            # enqueued one by one (bench.py latency_b1)
+            plan._uses = getattr(plan, "_uses", 0) + 1
+            if plan._uses >= 2:
+                plan.capture()
+        self._preprocess_into(plan, images_u8, valid_hw, layout_hwc)
+        plan.run()
+        self._last_head = plan.head
+        if getattr(self.cfg.ENGINE, "CHECK_FINITE", False):
+            # the FPN maps first: behind them GroupNorm-on-load computes max(a x + b, 0), which turns a NaN into 0 again
+            hd = plan.head
+            for l, ft in enumerate(plan.features):
+                # the buffers of the head's mode: no center without center_pred, chain output of the iterative head
+                for nme, t in (("FPN map", ft.t), ("logits", hd.logits[l]), ("delta / ctrness", hd.delta_ctr[l]),
+                               ("center", hd.center[l] if hd.center is not None else None),
+                               ("corners", hd.corners[l] if hd.corners is not None else None)):
+                    if t is not None and not bool(torch.isfinite(t).all()):
+                        raise _lib.DafneHipError("ENGINE.CHECK_FINITE: non-finite %s at level %d (weights / input overflow? a NaN "
+                                                 "accumulator of a non-ReLU layer turns into -inf)" % (nme, l))
+        return self.proposal_generator.dafne_outputs.predict_packed(
+            head_levels(plan.head, self.proposal_generator.fpn_strides), sizes=sizes, scale_corners=do_postprocess)
+
+    def _pipe_state(self, n, hn, wn, splits, even, device):
+        """The sub-batch pipeline of one batch shape, built on first use: {"plans": the plan sets (one DensePlan per sub-batch
+        each), "ho": each set's head outputs, "cand": its candidate buffer, "done": the event behind its last post-process, "runs":
+        its graph-path steps so far, "cs": the compute streams, "bounds": the sub-batches' image ranges, "i": steps so far}."""
+        def build():
+            nc = self.proposal_generator.dafne_head.num_classes
+            bounds = [(k * n) // splits for k in range(splits + 1)] if even else subbatch_bounds(n, splits)
+            # complete plan sets, each with its own head-output buffers: decode + NMS of call i run on the side stream while
+            # call i+1's convolutions already write the next set
+            nsets = 2 if splits > 1 else B1_PLAN_SETS
+            hos, plan_sets = [], []
+            for _ in range(nsets):
+                ho = engine.HeadOutputs(n, hn, wn, nc, self._weights()["scales"], self.device,
+                                        head_mode=self._weights()["head_mode"])
+                hos.append(ho)
+                plan_sets.append([engine.DensePlan(self._weights(), bounds[k + 1] - bounds[k], hn, wn, self.depth,
+                                                   nc, self.device, head_outputs=ho.views(bounds[k], bounds[k + 1]),
+                                                   shared_gpu=True)
+                                  for k in range(splits)])
+            # compute streams are high-priority: ROCm maps normal-priority streams onto a small shared set
+            # of hardware queues, and two sub-batches landing on one queue serialise (dense part alone,
+            # 4 splits: 714 -> 960 img/s); the high-priority pool gives each its own queue.  With the
+            # post-process stream in the mix 3 splits measured best (scratch/split_sweep.sh)
+            return {"i": 0, "cs": [_shared_stream(device, "compute", k) for k in range(splits)], "ho": hos,
+                    "plans": plan_sets, "bounds": bounds, "cand": [None] * nsets, "done": [None] * nsets, "runs": [0] * nsets}
+        key = (n, hn, wn, splits, "even") if (even and splits > 1) else (n, hn, wn, splits)
+        built = key not in self._pipe
+        st = self._lru_get(self._pipe, key, build)
+        if built:
+            # plan building enqueued buffer fills, weight packing and uploads on the caller's stream: finished before any
+            # sub-batch stream touches the plans (once per shape; the steps themselves never wait for the host).  The
+            # streams are ordered behind it by `inputs_ready` as well; this makes a new shape's first step independent of it
+            torch.cuda.synchronize(device)
+        return st
+
+    def _enqueue_dense(self, st, slot, cs, defer, graphs):
+        """The dense launches of plan set `slot`, one sub-batch per stream of `cs`.  -> defer: an event per stream where its head
+        towers begin.  graphs (hip_graphs_on): every sub-batch's ~200 launches replayed from ONE HIP graph per stream (kernels,
+        arguments and buffers of a plan are static) -- two graphs in the deferred form, split at the head towers: ~10 host
+        calls per step instead of ~600.  The launch order inside a stream is the plan's; across streams the hardware queues
+        interleave as before (the host runs many steps ahead either way)."""
+        plans, splits = st["plans"][slot], len(st["plans"][slot])
+        # A plan set's FIRST step on the graph path always runs eagerly and graphs are captured from its second use on: ROCm
+        # binds a stream to a hardware queue at its first submission, and torch's capture stream, created first, took one of
+        # the few queues the three sub-batch streams need for themselves (measured: capture in the very first step
+        # left the whole process at 1010-1050 images/s, eager and graph steps alike; eager first: 1300 both ways).
+        if not graphs or st["runs"][slot] == 0:
             # layer-interleaved enqueue: launch j of every sub-batch before launch j+1, so that the
             # prologue / epilogue bubbles of one sub-batch's kernel are filled by another's
-            sp = [ctypes.c_void_p(s.cuda_stream) for s in cs]
             # (sub-batches of different sizes may differ by a launch: the library picks kernels by tile count)
-            genv = os.environ.get("DAFNE_HIP_GRAPHS")                # A/B runs: 1 / 0 overrides the config
-            want_graphs = self.cfg.ENGINE.HIP_GRAPHS if graphs is None else bool(graphs)
-            if (self.use_graphs or want_graphs or genv == "1") and genv != "0" and graphs is not False:
-                # every sub-batch's ~200 dense launches replayed from ONE HIP graph per stream (captured on first use: kernels,
-                # arguments and buffers of a plan are static): ~10 host calls per step instead of ~600.  The launch order
-                # inside a stream is the plan's; across streams the hardware queues interleave as before (the host runs
-                # many steps ahead either way).
-                # A plan set's FIRST step always runs eagerly and graphs are captured from its second use on: ROCm binds a
-                # stream to a hardware queue at its first submission, and torch's capture stream, created first, took one of
-                # the few queues the three sub-batch streams need for themselves (measured: capture in the very first step
-                # left the whole process at 1010-1050 images/s, eager and graph steps alike; eager first: 1300 both ways).
-                eager_first = st["runs"]
-                if eager_first[slot] == 0:
-                    tower_evs = self._enqueue_eager(plans, cs, sp, splits, defer)
-                elif defer:
-                    tower_evs = []
-                    for k in range(splits):
-                        with torch.cuda.stream(cs[k]):
-                            plans[k].capture_parts()
-                            plans[k].graph_parts[0].replay()
-                            e = torch.cuda.Event()
-                            e.record(cs[k])                   # this sub-batch is at its head towers
-                            tower_evs.append(e)
-                            plans[k].graph_parts[1].replay()
-                else:
-                    tower_evs = []
-                    for k in range(splits):
-                        if plans[k].graph is None:
-                            with torch.cuda.stream(cs[k]):
-                                plans[k].capture()
-                        with torch.cuda.stream(cs[k]):
-                            plans[k].graph.replay()
-                eager_first[slot] += 1
-            else:
-                tower_evs = self._enqueue_eager(plans, cs, sp, splits, defer)
-            if defer:
-                ends = []
-                for k in range(splits):
-                    ev = torch.cuda.Event()
-                    ev.record(cs[k])
-                    ends.append(ev)
-                prev = self.__dict__.get("_deferred")
-                self.__dict__["_deferred"] = {"st": st, "slot": slot, "ends": ends, "sizes": sizes, "do": do_postprocess, "main": main,
-                                              "strides": strides}
-                return self._run_deferred(prev, tower_evs) if prev is not None else None
+            tower_evs = self._enqueue_eager(plans, cs, [ctypes.c_void_p(s.cuda_stream) for s in cs], splits, defer)
+        elif defer:
+            tower_evs = []
             for k in range(splits):
-                mark("end", k, cs[k])
-            if post_per_split and splits > 1:
-                evs = []
-                for k in range(splits):
-                    ev = torch.cuda.Event()
-                    ev.record(cs[k])
-                    evs.append(ev)
-                with torch.cuda.stream(self.side_stream):
-                    parts = [None] * splits
-                    for k in sorted(range(splits), key=lambda q: (bounds[q + 1] - bounds[q], q)):      # the shortest sub-batch ends first
-                        lo, hi = bounds[k], bounds[k + 1]
-                        self.side_stream.wait_event(evs[k])
-                        cand = outs.decode_packed(head_levels(plans[k].head, strides), out=st["cand_split"][slot][k])
-                        st["cand_split"][slot][k] = cand
-                        parts[k] = outs.select_packed(cand, sizes=sizes[lo:hi], scale_corners=do_postprocess)
-                    res = (torch.cat([r for r, _ in parts]), torch.cat([c for _, c in parts]))
-                    done = torch.cuda.Event()
-                    done.record(self.side_stream)
-                st["done"][slot] = done
-                for t in res:
-                    t.record_stream(main)
-                return res
-            with torch.cuda.stream(self.side_stream):
-                for k in range(splits):
-                    ev = torch.cuda.Event()
-                    ev.record(cs[k])
-                    self.side_stream.wait_event(ev)
-                mark("dec0", 0, self.side_stream)
-                cand = outs.decode_packed(head_levels(st["ho"][slot], strides), out=st["cand"][slot])
-                st["cand"][slot] = cand
-                mark("dec1", 0, self.side_stream)
-                res = outs.select_packed(cand, sizes=sizes, scale_corners=do_postprocess)
-                mark("nms1", 0, self.side_stream)
-                done = torch.cuda.Event()
-                done.record(self.side_stream)
-            st["done"][slot] = done
-            for t in res:                     # allocated on the side stream, consumed on the caller's
-                t.record_stream(main)
-            return res
+                with torch.cuda.stream(cs[k]):
+                    plans[k].capture_parts()
+                    plans[k].graph_parts[0].replay()
+                    e = torch.cuda.Event()
+                    e.record(cs[k])                   # this sub-batch is at its head towers
+                    tower_evs.append(e)
+                    plans[k].graph_parts[1].replay()
+        else:
+            tower_evs = []
+            for k in range(splits):
+                if plans[k].graph is None:
+                    with torch.cuda.stream(cs[k]):
+                        plans[k].capture()
+                with torch.cuda.stream(cs[k]):
+                    plans[k].graph.replay()
+        if graphs:
+            st["runs"][slot] += 1
+        return tower_evs
+
+    def _post_process(self, st, slot, wait_events, sizes, do_postprocess, strides, main):
+        """Decode + rotated NMS + rescale of plan set `slot`'s whole batch on the side stream, behind `wait_events`.  ->
+        (rows, counts), produced on the side stream for a consumer on `main`."""
+        outs = self.proposal_generator.dafne_outputs
+        with torch.cuda.stream(self.side_stream):
+            for ev in wait_events:
+                self.side_stream.wait_event(ev)
+            cand = outs.decode_packed(head_levels(st["ho"][slot], strides), out=st["cand"][slot])
+            st["cand"][slot] = cand
+            res = outs.select_packed(cand, sizes=sizes, scale_corners=do_postprocess)
+            done = torch.cuda.Event()
+            done.record(self.side_stream)
+        st["done"][slot] = done
+        for t in res:                     # allocated on the side stream, consumed on the caller's
+            t.record_stream(main)
+        return res
 
     def detect_scenes(self, scenes, patch_size=1024, overlap=200, batch=8, layout_hwc=None, tasks=("task1",), scales=(1,),
                       resample="bicubic"):
@@ -596,27 +568,15 @@ class OneStageDetector(nn.Module):
     def _run_deferred(self, p, tower_evs):
         """Decode + rotated NMS + rescale of a deferred step on the side stream: behind that step's convolutions and behind
         `tower_evs` (the step after it has reached its head towers)."""
-        st, slot = p["st"], p["slot"]
-        outs = self.proposal_generator.dafne_outputs
-        with torch.cuda.stream(self.side_stream):
-            for ev in list(p["ends"]) + list(tower_evs):
-                self.side_stream.wait_event(ev)
-            cand = outs.decode_packed(head_levels(st["ho"][slot], p["strides"]), out=st["cand"][slot])
-            st["cand"][slot] = cand
-            res = outs.select_packed(cand, sizes=p["sizes"], scale_corners=p["do"])
-            done = torch.cuda.Event()
-            done.record(self.side_stream)
-        st["done"][slot] = done
-        for t in res:                     # allocated on the side stream, consumed on the caller's
-            t.record_stream(p["main"])
-        return res
+        return self._post_process(p.st, p.slot, list(p.wait_events) + list(tower_evs), p.sizes, p.do_postprocess, p.strides, p.main)
 
     def flush_deferred(self):
         """(rows, counts) of the last detect_packed(defer=True) call -- its post-process is enqueued now -- or None."""
-        p = self.__dict__.pop("_deferred", None)
+        p, self._deferred = self._deferred, None
         if p is not None:
             return self._run_deferred(p, ())
-        return self.__dict__.pop("_deferred_res", None)
+        res, self._deferred_res = self._deferred_res, None
+        return res
 
     def _pack_inputs(self, batched_inputs, staged=False):
         """list[{"image": uint8 CHW BGR, "height", "width"}] -> (device uint8 batch [n,3,H,W], valid (h, w) per image, requested
@@ -643,9 +603,9 @@ class OneStageDetector(nn.Module):
             # the staging copies below run on torch's intra-op pool; inference_on_dataset caps that pool for the duration of
             # the loop (utils.host.capped_torch_threads: with one worker per visible CPU the workers' spin-wait starves the HIP
             # runtime's completion threads -- 50-200 ms stalls every few batches, 107-170 images/s instead of 1085)
-            st = self.__dict__.get("_staging")
-            if st is None:
-                st = self.__dict__.setdefault("_staging", {"i": 0, "pin": [None, None], "free": [None, None], "dev": [None, None, None]})
+            if self._staging is None:
+                self._staging = {"i": 0, "pin": [None, None], "free": [None, None], "dev": [None, None, None]}
+            st = self._staging
             slot = st["i"] & 1
             st["i"] += 1
             need = n * 3 * H * W
@@ -698,12 +658,11 @@ class OneStageDetector(nn.Module):
             # scratch/fwd_sync_probe.py) -- the unequal three-way split of the streamed loop pays only where steps overlap.
             # Result-neutral: an image gets the same bits in any batch composition (DESIGN section 5,
             # test_an_image_gets_the_same_detections_in_any_batch)
-            # (round 6: the post-process per sub-batch, the short sub-batch's under the long one's convolutions -- detect_packed(
-            # post_per_split=True), DAFNE_FWD_PPS=1 -- measured 7.05-7.16 ms per call of 8 against 6.94 for this form (4+4, one
-            # whole-batch post-process): two decode / NMS passes cost more than the overlap returns; scripts/fwd_sync_probe.py)
-            pps = os.environ.get("DAFNE_FWD_PPS", "0") == "1"
+            # (round 6: the post-process per sub-batch, the short sub-batch's under the long one's convolutions, was tried and
+            # lost -- 7.05-7.16 ms per call of 8 against 6.94 for this form: two decode / NMS passes cost more than the overlap
+            # returns; profiles/NOTES_r06.md)
             rows, counts = self.detect_packed(batch, valid_hw=valid, out_hw=out_hw, do_postprocess=do_postprocess,
-                                              pipelined=True, splits=splits, even=not pps, post_per_split=pps)
+                                              pipelined=True, splits=splits, even=True)
             # the rows are produced on the side stream and the host needs them now: a HOST wait on that stream.  (A device-side
             # wait_stream of the caller's stream, followed by the read-back's own wait, cost 0.85 ms per call once all the
             # shared streams are bound: 7.70 against 6.84 ms per call of 8, scratch/fwd_phase_probe.py)
@@ -728,14 +687,11 @@ class OneStageDetector(nn.Module):
             raise NotImplementedError("training is outside the scope of the MI355X inference engine")
         splits = max(1, int(self.cfg.ENGINE.PIPELINE_SPLITS))
         batch, valid, out_hw = self._pack_inputs(batched_inputs, staged=True)
-        q = self.__dict__.setdefault("_stream_q", [])       # batches in flight, oldest first: [out_hw, packed results or None]
-        # a batch too small to split (the reference's own loop: ONE image per call, tools/plain_train_net.py:316-336) alternates
-        # between two compute streams, call by call: the convolutions of image i + 1 run beside those of image i on the other
-        # plan set -- at batch 1 a res4 block is 32 tiles for 256 CUs
+        q = self._stream_q
         rot = 0
-        if min(splits, len(batched_inputs)) == 1 and os.environ.get("DAFNE_B1_ROTATE", "1") != "0":
-            rot = self.__dict__.get("_stream_rot", 0)
-            self.__dict__["_stream_rot"] = (rot + 1) % max(1, int(os.environ.get("DAFNE_B1_STREAMS", "3")))
+        if B1_ROTATE and min(splits, len(batched_inputs)) == 1:        # a batch too small to split
+            rot = self._stream_rot
+            object.__setattr__(self, "_stream_rot", (rot + 1) % B1_STREAMS)        # (per image: see detect_packed's _deferred)
         res = self.detect_packed(batch, valid_hw=valid, out_hw=out_hw, do_postprocess=do_postprocess,
                                  pipelined=True, splits=splits, defer=True, stream_offset=rot)
         if res is not None:                                  # the previous call's batch: its post-process was enqueued just now
@@ -747,7 +703,7 @@ class OneStageDetector(nn.Module):
 
     def flush(self):
         """Outputs of the oldest forward_streamed() batch still in flight (None when there is none): call until None."""
-        q = self.__dict__.get("_stream_q") or []
+        q = self._stream_q
         if not q:
             return None
         if q[-1][1] is None:                                 # the newest batch's post-process has not been enqueued yet
@@ -760,7 +716,9 @@ class OneStageDetector(nn.Module):
         """The detection counts of a batch go to a pinned host buffer behind its NMS (4 bytes per image)."""
         rows, counts = res
         with torch.cuda.stream(self.side_stream):
-            ring = self.__dict__.setdefault("_counts_ring", {"i": 0, "buf": [None] * 4})
+            if self._counts_ring is None:
+                self._counts_ring = {"i": 0, "buf": [None] * 4}
+            ring = self._counts_ring
             ck = ring["i"] % 4                                  # four pinned buffers: up to three batches in flight + the one the
             ring["i"] += 1                                      # caller may still be reading; grown to the largest batch, sliced
             if ring["buf"][ck] is None or ring["buf"][ck].numel() < counts.numel() or ring["buf"][ck].dtype != counts.dtype:
@@ -812,18 +770,12 @@ class OneStageDetector(nn.Module):
         else:
             gts = [x["instances"] for x in batched_inputs]
             batch, valid, _ = self._pack_inputs(batched_inputs)
-        L = _lib.load()
         n, _, h, w = batch.shape
-        hn, wn = (h + 31) // 32 * 32, (w + 31) // 32 * 32
-        mean = (ctypes.c_float * 3)(*[float(v) for v in self.cfg.MODEL.PIXEL_MEAN])
-        std = (ctypes.c_float * 3)(*[float(v) for v in self.cfg.MODEL.PIXEL_STD])
         outs = self.proposal_generator.dafne_outputs
         with torch.cuda.device(batch.device):
             batch = batch.contiguous()
-            plan = self.plan(n, hn, wn, slot=_slot)       # its own buffers: a detection call in flight keeps its head outputs
-            vt = None if all(tuple(v) == (h, w) for v in valid) else self._dev_const(valid, torch.int32, (n, 2))
-            _lib.check(L.dafne_preprocess_image_hip(_lib.ptr(batch), 0, n, h, w, _lib.ptr(vt), mean, std, hn, wn,
-                                                    _lib.ptr(plan.stem_in), _lib.current_stream()), "dafne_preprocess_image_hip")
+            plan = self.plan(n, _pad32(h), _pad32(w), slot=_slot)       # its own buffers: a detection call in flight keeps its head outputs
+            self._preprocess_into(plan, batch, valid)
             plan.run()
             levels = head_levels(plan.head, self.proposal_generator.fpn_strides)
             tg = outs.assign_targets([(lv.H, lv.W) for lv in levels], gts, self.device)

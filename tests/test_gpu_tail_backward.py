@@ -144,7 +144,7 @@ def test_backward_head_tail_end_to_end():
         assert torch.equal(p.grad, f)
     m.zero_grad(set_to_none=True)
     m.invalidate()
-    assert not hasattr(m, "_last_head_tail")
+    assert m._last_head_tail is None
 
 
 def test_sgd_loop_over_tail_parameters_lowers_the_loss():

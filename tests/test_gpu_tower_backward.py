@@ -119,7 +119,7 @@ def test_backward_towers_end_to_end():
         assert torch.equal(p.grad, f)
     m.zero_grad(set_to_none=True)
     m.invalidate()
-    assert not hasattr(m, "_last_towers")
+    assert m._last_towers is None
 
 
 def test_sgd_loop_over_tower_parameters_lowers_the_loss():

@@ -432,6 +432,7 @@ def test_deferred_post_process_gives_the_step_results_one_call_later(graphs):
     immediate form on the same batches -- eager launches and the two-part HIP graphs -- also across a change of shape and
     with an immediate call in between."""
     cfg, m = _gpu_model(splits=2)
+    declared = set(vars(m))
     g = torch.Generator().manual_seed(31)
     dev = torch.device("cuda", 0)
     batches = [torch.randint(0, 256, (4, 3, 128, 160), generator=g, dtype=torch.uint8).to(dev) for _ in range(5)]
@@ -464,3 +465,10 @@ def test_deferred_post_process_gives_the_step_results_one_call_later(graphs):
     assert torch.equal(r0[0, :int(c0[0])], want[0][0][0, :int(c0[0])]) and torch.equal(r1[0, :int(c1[0])], want[1][0][0, :int(c1[0])])
     with pytest.raises(ValueError):
         m.detect_packed(batches[0], defer=True)
+    # every piece of runtime state is declared at construction (none is created on first use), and invalidate() empties it
+    assert set(vars(m)) == declared
+    assert m.detect_packed(batches[0], pipelined=True, splits=2, graphs=graphs, defer=True) is None
+    torch.cuda.synchronize()
+    m.invalidate()                                         # drops the pending step with its plans
+    assert m.flush_deferred() is None and m.flush() is None
+    assert set(vars(m)) == declared

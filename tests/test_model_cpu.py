@@ -234,3 +234,21 @@ def test_subbatch_bounds_are_unequal_and_cover_the_batch():
             k = min(s, n)
             b = subbatch_bounds(n, k)
             assert b[0] == 0 and b[-1] == n and len(b) == k + 1 and all(b[i + 1] > b[i] for i in range(k)), (n, s, b)
+
+
+def test_hip_graph_decision_truth_table():
+    """one_stage_detector.hip_graphs_on: the one rule by which both the one-stream and the pipelined path of detect_packed decide
+    whether to replay from a HIP graph.  graphs=False always wins, then DAFNE_HIP_GRAPHS=0; otherwise graphs=True, the config key
+    or DAFNE_HIP_GRAPHS=1 each turn it on -- including the config-off, variable-set corner on the one-stream path."""
+    from dafne_amd.modeling.one_stage_detector import hip_graphs_on
+    table = {  # (graphs, cfg.ENGINE.HIP_GRAPHS, DAFNE_HIP_GRAPHS) -> replay from a graph?
+        (None, False, None): False, (None, False, "0"): False, (None, False, "1"): True,
+        (None, True, None): True, (None, True, "0"): False, (None, True, "1"): True,
+        (False, False, None): False, (False, False, "0"): False, (False, False, "1"): False,
+        (False, True, None): False, (False, True, "0"): False, (False, True, "1"): False,
+        (True, False, None): True, (True, False, "0"): False, (True, False, "1"): True,
+        (True, True, None): True, (True, True, "0"): False, (True, True, "1"): True,
+    }
+    assert len(table) == 18
+    for (graphs, cfg_on, env), want in table.items():
+        assert hip_graphs_on(graphs, cfg_on, env) is want, (graphs, cfg_on, env)
