@@ -102,14 +102,25 @@ def test_decode_candidates_vs_oracle_all_levels():
             assert n == exp["scores"].shape[0]
             gk = _key(cand.levels[im, :n].cpu().numpy(), cand.locs[im, :n].cpu().numpy(), cand.classes[im, :n].cpu().numpy())
             ek = _key(exp["fpn_levels"], exp["locations"], exp["pred_classes"])
+            gs, es = cand.scores[im, :n].cpu().numpy(), exp["scores"]
+            gi, ei = np.arange(n), np.arange(n)
             if not np.array_equal(gk, ek):
-                # only candidates within rounding distance of the cut may differ
+                # expf vs numpy exp may move a score by an ulp across a level's cut: the symmetric difference must be a handful
+                # of entries whose scores sit at the cut value of their level (a level that was cut reports topk rows)
                 diff = np.setxor1d(gk, ek)
                 assert len(diff) <= 4, len(diff)
-                continue
-            assert np.abs(cand.scores[im, :n].cpu().numpy() - exp["scores"]).max() < 1e-6
-            assert np.abs(cand.corners[im, :n].cpu().numpy() - exp["pred_corners"]).max() < TOL
-            assert np.abs(cand.hbox[im, :n].cpu().numpy() - exp["pred_boxes"]).max() < TOL
+                for k_ in diff:
+                    lvl = int(k_ >> 40)
+                    of_level = es[exp["fpn_levels"] == lvl]
+                    assert of_level.shape[0] == topk, (lvl, of_level.shape[0])
+                    cut = float(of_level.min())
+                    sc = gs[gk == k_] if k_ in gk else es[ek == k_]
+                    assert abs(float(sc[0]) - cut) <= 2e-7 * max(cut, 1e-30) + 1e-12, (int(k_), float(sc[0]), cut)
+                _, gi, ei = np.intersect1d(gk, ek, assume_unique=True, return_indices=True)    # the keys both sides share
+                assert gi.size >= n - 4 and np.all(np.diff(gi) > 0) and np.all(np.diff(ei) > 0)   # ... in the same order
+            assert np.abs(gs[gi] - es[ei]).max() < 1e-6
+            assert np.abs(cand.corners[im, :n].cpu().numpy()[gi] - exp["pred_corners"][ei]).max() < TOL
+            assert np.abs(cand.hbox[im, :n].cpu().numpy()[gi] - exp["pred_boxes"][ei]).max() < TOL
 
 
 def test_topk_ranks_below_threshold_scores_without_ctr_threshold():
