@@ -113,6 +113,16 @@ class UncookLevel(ctypes.Structure):
                 ("scale", c_float)]
 
 
+class SgdTensor(ctypes.Structure):
+    _fields_ = [("d_p", c_void_p), ("d_g", c_void_p), ("d_buf", c_void_p), ("n", c_i64), ("lr_factor", c_double),
+                ("weight_decay", c_float), ("form", c_i32), ("d_copy", c_void_p), ("d_addend", c_void_p), ("d_plain", c_void_p),
+                ("d_frag", c_void_p), ("d_frag16", c_void_p), ("d_wr", c_void_p), ("Cout", c_i32), ("Cin", c_i32), ("KH", c_i32),
+                ("KW", c_i32), ("row0", c_i32), ("rows", c_i32), ("reserved", c_i32 * 2)]
+
+
+SGD_NONE, SGD_F32, SGD_CONV = 0, 1, 2            # dafne_sgd_tensor.form (include/dafne_amd.h)
+
+
 # dafne_target_params.flags / dafne_loss_params.flags (include/dafne_amd.h)
 TGT_CENTER_SAMPLE, TGT_CENTER_SAMPLE_ONLY, TGT_COMBINE_CENTER_SAMPLE, TGT_IN_BOX_CHECK, TGT_LEVEL_SIZE_FILTERING, \
     TGT_FPN_STRIDE_NORM = 1, 2, 4, 8, 16, 32
@@ -256,6 +266,10 @@ SIGNATURES = {
     "dafne_train_gt_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dafne_train_gt_hip": (c_int, [ctypes.POINTER(TrainView), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6 +
                            [c_void_p, c_size_t, c_void_p]),
+    "dafne_sgd_num_chunks": (c_int, [ctypes.POINTER(SgdTensor), c_int]),
+    "dafne_sgd_table_bytes": (c_size_t, [ctypes.POINTER(SgdTensor), c_int]),
+    "dafne_sgd_table_build": (c_int, [ctypes.POINTER(SgdTensor), c_int, c_void_p, c_size_t]),
+    "dafne_sgd_step_hip": (c_int, [ctypes.POINTER(SgdTensor), c_int, c_void_p, c_size_t, c_double, c_double, c_int, c_int, c_void_p]),
 }
 
 

@@ -788,3 +788,6 @@ int dafne_tta_candidates_hip(const dafne_tta_view* views, int n_views, int n_ima
 
 // ------------------------------------------------ back through the finished regressions (dafne_head_uncook_backward_hip)
 #include "pred_backward_kernels.h"
+
+// ------------------------------------------------ SGD step that writes the packed weights in place (dafne_sgd_step_hip)
+#include "solver_kernels.h"

@@ -1052,6 +1052,66 @@ int dafne_train_gt_hip(const dafne_train_view* views, int n_views, const float* 
                        const int32_t* d_offsets_in, int G, int sort, float* d_corners, float* d_hbox, float* d_area,
                        int32_t* d_classes, int32_t* d_offsets_out, int32_t* d_src, void* d_ws, size_t ws_bytes, void* stream);
 
+/*
+ * SGD step on the device, packed compute copies written in place (csrc/solver_kernels.h; DESIGN row F14).  One launch updates every
+ * tensor of a table.  Per element, in fp32 (torch.optim.SGD with momentum, dampening 0, no Nesterov, bit for bit):
+ *     g'  = weight_decay == 0 ? g : fmaf(weight_decay, p, g)
+ *     buf = first_step ? g' : (momentum * buf) + g'          two roundings, not fused
+ *     p   = fmaf(-lr_t, buf, p)                              lr_t = (float)(lr * lr_factor), the product in double
+ *     g   = 0                                                when zero_grad
+ * d_p / d_g / d_buf hold n fp32 each (d_buf is not read on the first step).  `form` says which compute copy follows the new p:
+ *   DAFNE_SGD_NONE  none.
+ *   DAFNE_SGD_F32   d_copy[i] = p[i], or p[i] + d_addend[i] (fp32, one rounding) when d_addend is given: a convolution bias at
+ *                   its row offset inside pack_conv's [Cout_pad] bias (the caller passes the offset pointer; padding rows are
+ *                   not touched), a GroupNorm affine, a level scale into the buffer the host reads back.
+ *   DAFNE_SGD_CONV  p is an OIHW weight [Cout, Cin, KH, KW], Cin % 64 == 0, KH * KW <= 9.  Rounded to bf16 (nearest even on
+ *                   the bits as tensor.to(bfloat16): subnormals kept, NaN -> 0x7FC0) it goes to rows row0 .. row0 + Cout of the
+ *                   packed matrix d_plain [rows, K] bf16, K = Cin * KH * KW, column (c / 64) * 64 * KH * KW + (kh * KW + kw) * 64 +
+ *                   c % 64 (engine.pack_conv), and to every fragment-major form given (rows % 256 == 0 then), all in 16-byte
+ *                   groups g = 8 columns 8 * kg .. + 8 of row r:
+ *                     d_frag, d_wr [rows/256][8 waves][K/16][2][32 rows][8]: group ((((r >> 5) * (K/16) + kg / 2) * 2 + kg % 2) * 32 +
+ *                       r % 32)  (engine.pack_conv3x3_frag / pack_conv_frag);
+ *                     d_frag16 [rows/256][8 waves][K/32][2][4][16 rows][8]: group (((((r >> 5) * (K/32) + kg / 4) * 2 + (r >> 4) % 2) *
+ *                       4 + kg % 4) * 16 + r % 16)  (engine.pack_conv3x3_frag16).
+ *                   Two tensors may share one packed matrix at different row0 (corners_pred rows 0..7, ctrness row 8).  All
+ *                   pointers of a CONV tensor are 16-byte aligned.
+ * The table: dafne_sgd_table_build writes into HOST memory the image the kernel reads -- the n_tensors descriptors, then one
+ * 16-byte entry per chunk (16 rows x one 64-channel slab of a CONV tensor; 1024 elements otherwise; dafne_sgd_num_chunks of
+ * them, the launch's workgroups) -- dafne_sgd_table_bytes bytes.  The caller uploads it once, 16-byte aligned, and again only
+ * when a descriptor changes.  dafne_sgd_step_hip takes the same HOST descriptors (checked at every call) and the device image.
+ * A descriptor the kernel cannot serve -- a NULL d_p / d_g / d_buf / d_copy / d_plain, n <= 0 or not Cout * Cin * KH * KW, an
+ * unknown form, rows outside the packed matrix, a misaligned pointer (DAFNE_E_INVALID), Cin % 64 != 0, more than 9 taps, a
+ * fragment form on a matrix that is no multiple of 256 rows (DAFNE_E_UNSUPPORTED) -- makes every call here fail (num_chunks:
+ * -1, table_bytes: 0) with the message set; nothing is launched and no buffer changes.  Vector stores only, every output
+ * element has one writer: equal bits from run to run.
+ */
+#define DAFNE_SGD_NONE 0
+#define DAFNE_SGD_F32 1
+#define DAFNE_SGD_CONV 2
+typedef struct dafne_sgd_tensor {
+    float* d_p;                   /* master parameter, n fp32 */
+    float* d_g;                   /* gradient */
+    float* d_buf;                 /* momentum buffer */
+    int64_t n;
+    double lr_factor;             /* lr_t = (float)(lr * lr_factor) */
+    float weight_decay;
+    int32_t form;                 /* DAFNE_SGD_* */
+    float* d_copy;                /* F32: the fp32 compute copy */
+    const float* d_addend;        /* F32: optional, copy = p + addend */
+    void* d_plain;                /* CONV: packed bf16 matrix [rows, K] (row 0) */
+    void* d_frag;                 /* CONV: optional fragment-major forms of the WHOLE matrix */
+    void* d_frag16;
+    void* d_wr;
+    int32_t Cout, Cin, KH, KW;
+    int32_t row0, rows;           /* first row of this tensor in the packed matrix; rows of that matrix (Cout_pad) */
+    int32_t reserved[2];
+} dafne_sgd_tensor;
+int dafne_sgd_num_chunks(const dafne_sgd_tensor* tensors, int n_tensors);
+size_t dafne_sgd_table_bytes(const dafne_sgd_tensor* tensors, int n_tensors);
+int dafne_sgd_table_build(const dafne_sgd_tensor* tensors, int n_tensors, void* h_table, size_t table_bytes);
+int dafne_sgd_step_hip(const dafne_sgd_tensor* tensors, int n_tensors, const void* d_table, size_t table_bytes, double lr,
+                       double momentum, int first_step, int zero_grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

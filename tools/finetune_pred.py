@@ -14,6 +14,11 @@ with checkpoint.save_checkpoint (tools/eval_net.py --weights loads it).
 .9.bias; DESIGN row F12): OneStageDetector.tail_parameters through backward_head_tail.
 --towers (implies --tail): the whole of cls_tower and corners_tower, four convolutions and four GroupNorms each (DESIGN row F13):
 OneStageDetector.tower_parameters through backward_towers.  center_tower, the FPN and the backbone stay frozen.
+--device-solver: the step itself runs on the device as well (DESIGN row F14): dafne_amd.solver.DeviceSGD.from_cfg -- the
+reference's per-parameter rule over SOLVER.* (BASE_LR, BIAS_LR_FACTOR, WEIGHT_DECAY, WEIGHT_DECAY_NORM, WEIGHT_DECAY_BIAS, MOMENTUM;
+--lr / --weight-decay override BASE_LR / WEIGHT_DECAY) -- updates the parameters AND their packed copies in one launch, so the loop
+has no model.invalidate().  --lr-schedule: every step's learning rate from dafne_amd.solver.warmup_multistep_lr (SOLVER.STEPS,
+GAMMA, WARMUP_FACTOR, WARMUP_ITERS; BASE_LR, or --lr when given).
 """
 import argparse
 import json
@@ -32,8 +37,8 @@ def main(argv=None):
     ap.add_argument("--scene-dir", required=True, help="directory of scene images")
     ap.add_argument("--scene-labels", required=True, help="directory of the scenes' DOTA labelTxt files")
     ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--lr", type=float, default=0.001)
-    ap.add_argument("--weight-decay", type=float, default=0.0)
+    ap.add_argument("--lr", type=float, default=None, help="learning rate (default 0.001; with --device-solver: SOLVER.BASE_LR)")
+    ap.add_argument("--weight-decay", type=float, default=None, help="weight decay (default 0; with --device-solver: SOLVER.WEIGHT_DECAY)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8, help="tiles per step")
     ap.add_argument("--patch-size", type=int, default=1024)
@@ -42,6 +47,9 @@ def main(argv=None):
                                                         "cls_tower and corners_tower (backward_head_tail)")
     ap.add_argument("--towers", action="store_true", help="also train every convolution and GroupNorm of cls_tower and corners_tower "
                                                           "(backward_towers; implies --tail)")
+    ap.add_argument("--device-solver", action="store_true", help="step on the device and update the packed weights in place "
+                                                                 "(solver.DeviceSGD.from_cfg); no invalidate() in the loop")
+    ap.add_argument("--lr-schedule", action="store_true", help="each step's learning rate from solver.warmup_multistep_lr")
     ap.add_argument("--out", required=True, help="checkpoint to write")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides")
     args = ap.parse_args(argv)
@@ -83,17 +91,34 @@ def main(argv=None):
         params, backward = model.tail_parameters(), model.backward_head_tail
     else:
         params, backward = model.prediction_parameters(), model.backward_prediction_layers
-    opt = torch.optim.SGD(params, lr=args.lr, momentum=float(cfg.SOLVER.get("MOMENTUM", 0.9)), weight_decay=args.weight_decay)
+    from dafne_amd.solver import DeviceSGD, warmup_multistep_lr
+    if args.device_solver:
+        opt = DeviceSGD.from_cfg(model, params, cfg, lr=args.lr, weight_decay=args.weight_decay)
+    else:
+        opt = torch.optim.SGD(params, lr=0.001 if args.lr is None else args.lr, momentum=float(cfg.SOLVER.get("MOMENTUM", 0.9)),
+                              weight_decay=0.0 if args.weight_decay is None else args.weight_decay)
+    sched_cfg = cfg
+    if args.lr_schedule and args.lr is not None:
+        sched_cfg = cfg.clone()
+        sched_cfg.SOLVER.BASE_LR = args.lr
     stream = scene_train_batches(cfg, scenes, labels, batch=args.batch, seed=args.seed, patch_size=args.patch_size,
                                  overlap=args.overlap, device=dev)
     with torch.cuda.device(dev):
         for step, tb in enumerate(stream):
             if step >= args.steps:
                 break
-            opt.zero_grad(set_to_none=True)
-            losses = backward(tb)
-            opt.step()
-            model.invalidate()
+            lr = warmup_multistep_lr(sched_cfg, step) if args.lr_schedule else None
+            if args.device_solver:
+                losses = backward(tb)
+                opt.step(lr=lr)             # zeroes the gradients in the same pass
+            else:
+                if lr is not None:
+                    for g in opt.param_groups:
+                        g["lr"] = lr
+                opt.zero_grad(set_to_none=True)
+                losses = backward(tb)
+                opt.step()
+                model.invalidate()
             print(json.dumps(dict({"step": step, "tiles": len(tb)}, **{k: float(v) for k, v in sorted(losses.items())})))
     save_checkpoint(model, args.out)
     print("wrote %s" % args.out)
